@@ -8,7 +8,19 @@ view of 1M synthetic Gaussians (SH degree 3, require_depth=True, the state
 after iteration 7000).  Inputs are activated tensors already resident in HBM;
 losses, optimiser and the Python getters are outside the step.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C5] [--no-depth] [--forward-only]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                  [--config C2|C3|C5] [--no-depth] [--forward-only]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with
+the contract fields (`value`, `ms_per_step`, ...) and the workload; nothing
+else touches the GPU.  --full adds everything else to the same line: the
+per-stage table and the dominant kernel's `roofline`, the instance counts of
+the view, the `cpu_baseline` and, with N > 1, the `dist` object (all described
+below).  --dump-outputs DIR writes what the last timed step handed its caller
+(the five forward outputs and, unless forward only, every gradient) as
+DIR/<name>.npy in float32, a fixed seeded sample of the larger arrays so the
+files stay under 64 MB together; the inputs are seeded, so two builds run with
+the same arguments can be compared file by file.
 
 --config C2 is BASELINE.json configs[1] (100k Gaussians, one 800x800 view,
 forward only); --no-depth is require_depth=False (training iterations <
@@ -26,10 +38,10 @@ from the per-view DC rows and camera centres (2.6x fewer xGMI bytes at SH 3);
 allreduce` all-reduces every row.  `value` =
 views/s over all ranks, time = max over ranks.
 
-Rank 0 prints one JSON line: the contract fields, a `roofline` object for the
+Rank 0 prints one JSON line: the contract fields and, with --full, a `roofline` object for the
 dominant kernel (algorithmic bytes per launch / its HIP-event-timed average
 duration in the timed region, vs 8 TB/s HBM peak; `traffic` from the
-committed rocprofv3 PMC summary when present).  Inside the timed region only
+committed rocprofv3 PMC summary when present).  With --full, inside the timed region only
 the dominant stage is bracketed by hipEvents (each recorded event idles the
 stream ~10 us); the other stages' times come from --stage-steps untimed steps
 with every stage bracketed and a `cpu_baseline` object (the C oracle on the host
@@ -64,8 +76,32 @@ VALU_PEAK_CYCLES = 2
 TRANS_PEAK_CYCLES = 4
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every tensor of `arrays` that holds something as outdir/<name>.npy in float32
+    (an absent or empty one, such as the SG gradients at SG degree 0, gets no file: there is nothing
+    to compare).  The byte budget is split evenly over them; one that fits its share is written whole
+    in its own shape, a larger one as the flat sample at sorted indices drawn (with replacement) from
+    a generator seeded by the array's name, so the same name and size always give the same elements."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: v.detach() for k, v in arrays.items() if v is not None and v.numel()}
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
 
 
 def launcher_cmd(argv, nproc: int, port: int):
@@ -153,6 +189,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what the headline figure does not need: the per-stage table, "
+                         "the roofline of the dominant kernel, the view's instance counts, the CPU baseline and "
+                         "(N > 1) the exchange timed apart")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and gradients as DIR/<name>.npy (float32; the "
+                         "larger arrays as a fixed seeded sample, under 64 MB together)")
     ap.add_argument("--config", choices=["C2", "C3", "C5"], default="C3",
                     help="C3: 1M Gaussians, SH 3 (the metric's config); C5: 5M Gaussians, SH 3 + SG 7; "
                          "C2: 100k Gaussians, 800x800, forward only")
@@ -163,7 +206,7 @@ def parse():
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--sg-degree", type=int, default=None)
     ap.add_argument("--no-depth", action="store_true", help="require_depth=False (iterations < 7000)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--exchange", choices=["overlap", "factored", "allreduce"], default="overlap",
                     help="N > 1: gradient exchange: gsr_dist.OverlappedViewGrads (inside the backward, range by "
                          "range), FactoredViewGrads (after it), or an all-reduce of every row")
@@ -640,6 +683,8 @@ def main():
     if args.e2e:
         if world > 1:
             raise SystemExit("bench.py --e2e runs on one GPU")
+        if args.dump_outputs:
+            raise SystemExit("bench.py --e2e has no --dump-outputs (the raster step's outputs: run without --e2e)")
         return run_e2e(args, dev)
     if world > 1:
         torch.cuda.set_device(dev)
@@ -696,10 +741,11 @@ def main():
     def step():
         if args.forward_only:  # the forward alone: no autograd graph, nothing saved for a backward
             with torch.no_grad():
-                state["radii"] = rasterizer(
+                state["out"] = rasterizer(
                     means3D=params["means3D"], means2D=means2D, opacities=params["opacities"], shs=params["shs"],
                     sg_axis=params["sg_axis"], sg_sharpness=params["sg_sharpness"], sg_color=params["sg_color"],
-                    scales=params["scales"], rotations=params["rotations"])[1]
+                    scales=params["scales"], rotations=params["rotations"])
+            state["radii"] = state["out"][1]
             return
         for t in list(params.values()) + [means2D]:
             t.grad = None
@@ -707,6 +753,7 @@ def main():
             means3D=params["means3D"], means2D=means2D, opacities=params["opacities"], shs=params["shs"],
             sg_axis=params["sg_axis"], sg_sharpness=params["sg_sharpness"], sg_color=params["sg_color"],
             scales=params["scales"], rotations=params["rotations"])
+        state["out"] = (color, radii, mdepth, alpha, normal)  # what the caller receives (--dump-outputs)
         outs, gs = [color], [g_color]
         if geom:
             outs += [mdepth, normal]
@@ -724,20 +771,21 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    # per-stage table: a few untimed steps with every stage bracketed by events
-    _C.timing_collect()  # discard
-    _C.timing_stages(None)
-    _C.timing_enable(True)
-    for _ in range(max(1, args.stage_steps)):
-        step()
-    torch.cuda.synchronize(dev)
-    _C.timing_enable(False)
-    table = _C.timing_collect()
-    table_ms = {k: (ms / n if n else 0.0) for k, (ms, n) in table.items()}
-    dom = max(table_ms, key=lambda k: table_ms[k])
-    # timed region: events only around the dominant stage (the roofline kernel)
-    _C.timing_stages(None if args.all_stage_events else [dom])
-    _C.timing_enable(True)
+    if args.full:
+        # per-stage table: a few untimed steps with every stage bracketed by events
+        _C.timing_collect()  # discard
+        _C.timing_stages(None)
+        _C.timing_enable(True)
+        for _ in range(max(1, args.stage_steps)):
+            step()
+        torch.cuda.synchronize(dev)
+        _C.timing_enable(False)
+        table = _C.timing_collect()
+        table_ms = {k: (ms / n if n else 0.0) for k, (ms, n) in table.items()}
+        dom = max(table_ms, key=lambda k: table_ms[k])
+        # timed region: events only around the dominant stage (the roofline kernel)
+        _C.timing_stages(None if args.all_stage_events else [dom])
+        _C.timing_enable(True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -748,13 +796,37 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    _C.timing_enable(False)
-    _C.timing_stages(None)
-    stages = _C.timing_collect()
+    if args.full:
+        _C.timing_enable(False)
+        _C.timing_stages(None)
+        stages = _C.timing_collect()
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         _max_over_ranks(t)
         elapsed = float(t.item())
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * args.steps / elapsed
+    if args.dump_outputs:  # the last timed step's outputs and (summed, N > 1) gradients; rank r > 0 under rank<r>/
+        arrays = dict(zip(("color", "radii", "mdepth", "alpha", "normal"), state["out"]))
+        if not args.forward_only:
+            arrays.update({"grad_" + k: params[k].grad for k in grad_keys}, grad_means2D=means2D.grad)
+        dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"), arrays)
+    line = {
+        "metric": "train iters/sec (fwd+bwd raster) at 1080p, 1M Gaussians; HBM GB/s vs peak",
+        "value": round(value, 3), "unit": "forward iters/s" if args.forward_only else "iters/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
+        "dump_outputs": args.dump_outputs,
+        "config": {"workload": workload, "P": P, "width": W, "height": H, "sh_degree": args.sh_degree,
+                   "sg_degree": args.sg_degree, "require_depth": geom,
+                   "parallelism": f"view-parallel dp{world}" if world > 1 else "single"},
+    }
+    if not args.full:  # a plain run ends here
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     dist_info = None
     if world > 1:  # the exchange's cost: the same steps without it, and its collectives alone
         if overlap is not None:
@@ -801,8 +873,6 @@ def main():
         E_rows = row_entries(plist_, ranges_, (W + 15) // 16)
         del plist_, ranges_
         K_contrib = int(_C.debug_max_contrib(fo[9], H, W).astype("int64").sum())
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * args.steps / elapsed
     shm = (args.sh_degree + 1) ** 2
     algo = stage_bytes(P, K, K_live, W * H, shm, args.sg_degree, geom, K_contrib, E_rows)
     algo_upper = stage_bytes(P, K, K_live, W * H, shm, args.sg_degree, geom, None, E_rows)
@@ -856,20 +926,10 @@ def main():
         except Exception as e:  # noqa: BLE001 - report, never hide
             cpu = {"value": None, "error": repr(e)}
     if rank == 0:
-        line = {
-            "metric": "train iters/sec (fwd+bwd raster) at 1080p, 1M Gaussians; HBM GB/s vs peak",
-            "value": round(value, 3), "unit": "forward iters/s" if args.forward_only else "iters/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "P": P, "width": W, "height": H, "sh_degree": args.sh_degree,
-                       "sg_degree": args.sg_degree, "require_depth": geom, "num_rendered": int(K), "instances_after_tile_culling": K_live,
-                       "instances_to_max_contributor": K_contrib,
-                       "parallelism": f"view-parallel dp{world}" if world > 1 else "single",
-                       "step_algorithmic_GBps": round(total_algo / (ms_per_step * 1e-3) / 1e9, 2)},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "dist": dist_info,
-        }
+        line["config"].update(num_rendered=int(K), instances_after_tile_culling=K_live,
+                              instances_to_max_contributor=K_contrib,
+                              step_algorithmic_GBps=round(total_algo / (ms_per_step * 1e-3) / 1e9, 2))
+        line.update(roofline=roofline, cpu_baseline=cpu, dist=dist_info)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

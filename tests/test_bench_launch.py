@@ -70,6 +70,62 @@ def test_rccl_launch_refuses_more_ranks_than_devices():
     assert "RCCL needs 2 devices" in r.stderr
 
 
+def test_full_and_dump_outputs_are_off_by_default():
+    a = _args("--gpus", "1", "--steps", "3", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    a = _args("--full", "--dump-outputs", "somewhere")
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """Small arrays whole and in shape, a large one as the same seeded sample on every call, integer
+    outputs as float32, absent gradients left out, and the files together inside the byte budget."""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)  # 1000 elements over 2 non-empty arrays
+    big = torch.arange(10_000, dtype=torch.float64).reshape(100, 100)
+    arrays = {"big": big, "radii": torch.arange(6, dtype=torch.int32).reshape(2, 3), "empty": torch.zeros(0, 3),
+              "none": None}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), {"radii": arrays["radii"], "big": big + 0.0, "empty": arrays["empty"]})
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["big.npy", "radii.npy"]  # no file for an absent or empty array
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["radii.npy"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    s = got["big.npy"]
+    assert s.shape == (500,) and np.all(np.diff(s) >= 0) and s.min() >= 0 and s.max() < 10_000
+    assert len(np.unique(s)) > 400  # a spread sample, not one block
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(v.nbytes for v in got.values()) <= 4000
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_contract_line_and_dumps_outputs(tmp_path):
+    """A plain run (small scene): --steps sets the timed steps, the line holds the contract fields and
+    none of what --full measures, and --dump-outputs leaves the outputs and gradients of the last step."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--P", "3000", "--width", "130", "--height", "70", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    (line,) = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "iters/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 1.0) < 1e-2
+    assert not {"roofline", "cpu_baseline", "dist"} & set(line)
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert {"color", "radii", "mdepth", "alpha", "normal", "grad_means3D", "grad_means2D", "grad_shs",
+            "grad_opacities", "grad_scales", "grad_rotations"} <= set(got)
+    assert got["color"].shape == (3, 70, 130) and got["grad_shs"].shape == (3000, 16, 3)
+    assert all(v.dtype == np.float32 and v.size and np.isfinite(v).all() for v in got.values())
+    assert not {"grad_sg_axis", "grad_sg_sharpness", "grad_sg_color"} & set(got)  # SG degree 0: empty, no file
+    assert np.abs(got["color"]).max() > 0 and np.abs(got["grad_means3D"]).max() > 0 and got["radii"].max() > 0
+    assert sum(v.nbytes for v in got.values()) <= 64e6
+
+
 def test_launcher_starts_n_ranks(tmp_path):
     """The real child launch (gloo, CPU): two ranks start, see WORLD_SIZE = 2
     and rank 0 prints the line."""

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 tail -1 $O/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 300 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err || exit 1
+timeout -k 10 300 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err || exit 1
 cut -c1-200 $O/bench_c3.json
 timeout -k 10 300 python bench.py --e2e --steps 30 --warmup 5 > $O/bench_e2e.json 2> $O/bench_e2e.err || exit 1
 cut -c1-200 $O/bench_e2e.json

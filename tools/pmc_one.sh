@@ -6,4 +6,4 @@ OUT=$ROOT/gpurun_out/$1
 shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 120 rocprofv3 --pmc "$@" --output-format csv -d $OUT -o run -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc.log 2>&1
+timeout -s KILL 120 rocprofv3 --pmc "$@" --output-format csv -d $OUT -o run -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc.log 2>&1

@@ -20,8 +20,8 @@ cd /tmp && export TMPDIR=/tmp
 # an SQ pass whose counter set the profiler rejects (exit 1) is recorded and skipped; a time limit,
 # abort or crash (any other status) stops the script
 soft() { if [ "$1" -eq 1 ]; then echo "pass failed (status 1), skipped" >&2; return 0; fi; return "$1"; }
-BENCH="$ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline $WL"
-SHORT="$ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --stage-steps 1 $WL"
+BENCH="$ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $WL"
+SHORT="$ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --stage-steps 1 $WL"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $BENCH > $OUT/trace.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python3 $SHORT > $OUT/fetch.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- python3 $SHORT > $OUT/write.log 2>&1 && \
