@@ -59,9 +59,7 @@ size_t scan_temp_bytes(int P) {
 
 // rocPRIM picks a merge sort below 1M items for 32-bit keys (10 merge passes
 // at P = 1M); a merge-sort limit of 0 keeps the 4-pass onesweep radix sort.
-#ifndef GSR_DSORT_BITS
-#define GSR_DSORT_BITS 8  // 0: rocPRIM's tuned onesweep config; measured at C3: 8 / 512 x 16 0.127 ms vs tuned 0.147 (11 bits: 0.145-0.173, 7: 0.177)
-#endif
+constexpr unsigned kDsortBits = 8;  // measured at C3: 8 / 512 x 16 0.127 ms vs rocPRIM's tuned onesweep config 0.147 (11 bits: 0.145-0.173, 7: 0.177)
 // Keys per onesweep block, measured at C3 (depth_order): 1024 x 4 0.104 ms, 512 x 8 0.112, 1024 x 3 0.117,
 // 1024 x 8 0.117, 512 x 12 0.120, 512 x 16 0.126, 1024 x 2 0.129, 256 x 12 0.134, 1024 x 6 0.137, 512 x 20 0.142,
 // 256 x 8 0.145, 256 x 16 0.148, 512 x 6 0.153.
@@ -71,13 +69,9 @@ size_t scan_temp_bytes(int P) {
 #ifndef GSR_DSORT_ITEMS
 #define GSR_DSORT_ITEMS 4
 #endif
-#if GSR_DSORT_BITS
 using DepthOnesweep = rocprim::radix_sort_onesweep_config<rocprim::kernel_config<256, 12>,
                                                           rocprim::kernel_config<GSR_DSORT_BLOCK, GSR_DSORT_ITEMS>,
-                                                          GSR_DSORT_BITS, rocprim::block_radix_rank_algorithm::match>;
-#else
-using DepthOnesweep = rocprim::default_config;
-#endif
+                                                          kDsortBits, rocprim::block_radix_rank_algorithm::match>;
 using DepthSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
                                                    DepthOnesweep, 0>;
 

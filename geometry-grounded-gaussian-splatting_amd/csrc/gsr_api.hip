@@ -242,7 +242,9 @@ size_t carve_point_binning(void* base, int PN, uint32_t tiles, PointBinState& s)
     s.keys_unsorted = c.take<uint32_t>(PN);
     s.keys = c.take<uint32_t>(PN);
     s.pt_list = c.take<uint32_t>(PN);
-    s.sort_tmp_bytes = point_sort_temp_bytes(PN, tiles);
+    // (the retired point sort's key output and temporaries: `keys` and the empty `sort_tmp` stay carved, so
+    // the buffer's size and offsets are what callers have sized it for)
+    s.sort_tmp_bytes = 0;
     s.sort_tmp = c.take<char>(s.sort_tmp_bytes);
     return c.off + 256;
 }

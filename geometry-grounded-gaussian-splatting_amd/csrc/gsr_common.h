@@ -138,10 +138,10 @@ struct PointState {  // per point (point buffer)
     float* t;          // |p_view| (preprocessPointsCUDA ts, sample_forward.cu:50; integrate / evaluate_sdf)
 };
 struct PointBinState {  // point binning buffer
-    uint32_t* keys_unsorted;  // tile of each point (num_tiles when culled: sorts last)
-    uint32_t* keys;
-    uint32_t* pt_list;        // point indices stably sorted by tile
-    void* sort_tmp;
+    uint32_t* keys_unsorted;  // tile of each point (num_tiles when culled: in no tile's range)
+    uint32_t* keys;           // (unused since the point sort was retired; kept for the buffer layout)
+    uint32_t* pt_list;        // point indices grouped by tile (sample_scatter_kernel)
+    void* sort_tmp;           // (empty, as keys)
     size_t sort_tmp_bytes;
 };
 struct SampleTiles {  // per tile, after TileState in the tile buffer

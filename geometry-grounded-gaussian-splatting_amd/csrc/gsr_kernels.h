@@ -121,7 +121,6 @@ hipError_t launch_point_fwd(int query, const FwdParams& p, const GeomState& gs, 
                             hipStream_t stream);
 
 // sample.hip
-size_t point_sort_temp_bytes(int PN, uint32_t tiles);
 hipError_t launch_sample_points(const FwdParams& p, int PN, const float* points3D, const PointState& ps,
                                 const PointBinState& pb, const SampleTiles& st, hipStream_t stream);
 hipError_t launch_sample_setup(int PN, uint32_t tiles, const PointBinState& pb, const SampleTiles& st,

@@ -14,7 +14,7 @@
 // 49 x (<= 4 + 4) gathers per pixel are served by L1/L2.  Divisions by the
 // homogeneous coordinate are one v_rcp_f32 per tap (the reference builds with
 // --use_fast_math, warp-patch-ncc/setup.py:18).
-// Round 5 (GSR_NCC_TAPS2): the taps' gathers are issued per group of 3-4 taps
+// Round 5: the taps' gathers are issued per group of 3-4 taps
 // before their arithmetic (the per-tap version waited on every tap's loads at
 // 2 waves per SIMD), the reference's per-tap division for K_r^-1 of the tap is
 // hoisted out of the rows, the homography-gradient dot product is folded to
@@ -52,9 +52,6 @@ __device__ __forceinline__ f3 operator-(f3 a, f3 b) { return {a.x - b.x, a.y - b
 __device__ __forceinline__ f3 operator*(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ float dot3(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
-#ifndef GSR_NCC_TAPS2
-#define GSR_NCC_TAPS2 1  // the folded tap loop (ncc_pixel); 0: the per-tap restatement
-#endif
 #ifndef GSR_NCC_WAVES
 #define GSR_NCC_WAVES 4  // waves per SIMD the NCC kernels are compiled for (<= 128 VGPRs)
 #endif
@@ -95,7 +92,6 @@ __device__ __forceinline__ NccPix ncc_pixel(const NccArgs& a, int ux, int uy, fl
         f3 g_n = {0.f, 0.f, 0.f}, g_n2 = {0.f, 0.f, 0.f}, g_rn = {0.f, 0.f, 0.f};
         const float* Ir = a.image_r;
         const float* In = a.image_n;
-#if GSR_NCC_TAPS2
         if (a.Wn < 3 || a.Hn < 3) {
             ok = false;  // (no warp can lie inside the margin; the taps below assume two columns and rows)
         } else {
@@ -202,58 +198,6 @@ __device__ __forceinline__ NccPix ncc_pixel(const NccArgs& a, int ux, int uy, fl
             g_n2 = f3{X2, Y2, Z2} * 2.f;
             g_rn = {X3, Y3, Z3};
         }
-#else
-        for (int dv = -kNccRadius; dv <= kNccRadius; dv++) {
-            const float dv_f = 0.5f * dv;
-            const bool odd_v = (dv & 1) != 0;
-            const int v0r = uy + (dv >> 1), v1r = v0r + (odd_v ? 1 : 0);  // floor / ceil of dv/2
-            const float w_v0 = odd_v ? 0.5f : 1.f, w_v1 = odd_v ? 0.5f : 0.f;
-            const f3 H_uc_v = H_uc + H[1] * dv_f;
-            const float right_y = (uy + dv_f - a.cy_r) / a.fy_r;
-#pragma unroll
-            for (int du = -kNccRadius; du <= kNccRadius; du++) {
-                const float du_f = 0.5f * du;
-                const bool odd_u = (du & 1) != 0;
-                const int u0r = ux + (du >> 1), u1r = u0r + (odd_u ? 1 : 0);
-                const float w_u0 = odd_u ? 0.5f : 1.f, w_u1 = odd_u ? 0.5f : 0.f;
-                // reference image at (u + du/2, v + dv/2): the taps of the reference's line cache
-                const float c00 = Ir[v0r * a.Wr + u0r];
-                const float c01 = odd_u ? Ir[v0r * a.Wr + u1r] : c00;
-                const float c10 = odd_v ? Ir[v1r * a.Wr + u0r] : 0.f;
-                const float c11 = (odd_v && odd_u) ? Ir[v1r * a.Wr + u1r] : 0.f;
-                const float c_r = (c00 * w_u0 + c01 * w_u1) * w_v0 + (c10 * w_u0 + c11 * w_u1) * w_v1;
-                // neighbour image at the warped position
-                const f3 H_uv = H_uc_v + H[0] * du_f;
-                const float rz = __builtin_amdgcn_rcpf(H_uv.z);
-                const float un = H_uv.x * rz, vn = H_uv.y * rz;
-                ok = ok && un - kNccHalfExtent > 0 && un + kNccHalfExtent < a.Wn - 1 && vn - kNccHalfExtent > 0 &&
-                     vn + kNccHalfExtent < a.Hn - 1;
-                const float fu = floorf(un), fv = floorf(vn);
-                const int u0 = min(max((int)fu, 0), a.Wn - 1), v0 = min(max((int)fv, 0), a.Hn - 1);
-                const int u1 = min(max((int)ceilf(nextafterf(un, INFINITY)), 0), a.Wn - 1);
-                const int v1 = min(max((int)ceilf(nextafterf(vn, INFINITY)), 0), a.Hn - 1);
-                const float c00n = In[v0 * a.Wn + u0], c01n = In[v0 * a.Wn + u1];
-                const float c10n = In[v1 * a.Wn + u0], c11n = In[v1 * a.Wn + u1];
-                const float wv0 = v1 - vn, wv1 = vn - v0, wu0 = u1 - un, wu1 = un - u0;
-                const float c_n = wv0 * (wu0 * c00n + wu1 * c01n) + wv1 * (wu0 * c10n + wu1 * c11n);
-                s_r += c_r;
-                s_n += c_n;
-                s_r2 += c_r * c_r;
-                s_n2 += c_n * c_n;
-                s_rn += c_r * c_n;
-                // d c_n / d(homography column combination) (warp_patch_ncc_impl.cu:208-224)
-                const float dcx = -c00n * wv0 + c01n * wv0 - c10n * wv1 + c11n * wv1;
-                const float dcy = -c00n * wu0 - c01n * wu1 + c10n * wu0 + c11n * wu1;
-                const f3 dH = {dcx * rz, dcy * rz, (-dcx * un - dcy * vn) * rz};
-                const f3 left = {dH.x * a.fx_n, dH.y * a.fy_n, dH.x * a.cx_n + dH.y * a.cy_n + dH.z};
-                const f3 right = {(ux + du_f - a.cx_r) / a.fx_r, right_y, 1.f};
-                const f3 ga = right * dot3(left, aux);
-                g_n = g_n + ga;
-                g_n2 = g_n2 + ga * (2.f * c_n);
-                g_rn = g_rn + ga * c_r;
-            }
-        }
-#endif
         constexpr float kInv = 1.f / 49.f;
         const float cross = s_rn - s_r * s_n * kInv;
         const float var_r = s_r2 - s_r * s_r * kInv;

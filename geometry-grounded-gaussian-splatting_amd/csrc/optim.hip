@@ -38,25 +38,16 @@ __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v,
     return p;
 }
 
-#ifndef GSR_ADAM_NT
 // Non-temporal loads and stores (each element is touched once per step, and the step's 1-2 GB pass through
 // the caches otherwise): bench_optim's full parameter set 0.576 -> 0.531 ms.  Two or four float4 per thread
 // per grid-stride step with all loads issued first measured slower (0.541 / 0.623 ms with these hints).
-#define GSR_ADAM_NT 1
-#endif
-
 typedef float adam_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
-    if constexpr (GSR_ADAM_NT) {
-        const adam_f4 v = __builtin_nontemporal_load(reinterpret_cast<const adam_f4*>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    } else {
-        return *p;
-    }
+    const adam_f4 v = __builtin_nontemporal_load(reinterpret_cast<const adam_f4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void st_stream(float4* p, float4 v) {
-    if constexpr (GSR_ADAM_NT) __builtin_nontemporal_store(adam_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<adam_f4*>(p));
-    else *p = v;
+    __builtin_nontemporal_store(adam_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<adam_f4*>(p));
 }
 
 __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a, float eps) {

@@ -95,9 +95,6 @@ __device__ inline void zero_outputs(const PreprocessBwdArgs& a, int idx) {
     }
 }
 
-#ifndef GSR_SG_UNROLL
-#define GSR_SG_UNROLL 1
-#endif
 // SG degree 7 (the configuration with SG lobes, BASELINE C5), all lobes of
 // a Gaussian at once: its axis / colour / sharpness rows (21 + 21 + 7
 // consecutive floats) are loaded and its gradient rows stored as wide
@@ -206,47 +203,30 @@ __device__ __forceinline__ void wave_load_rows(const float* __restrict__ g, floa
 // A wave's n consecutive rows of nf floats each, staged in LDS in the
 // global layout, written out as whole-wave 16-B pieces: one store
 // instruction covers 1 KB of consecutive bytes instead of 64 rows.
-// (GSR_PBWD_NT: non-temporal stores — the gradient rows are read next by the optimizer step, after the
+// (non-temporal stores: the gradient rows are read next by the optimizer step, after the
 // whole backward has streamed through the caches)
-#ifndef GSR_PBWD_NT
-#define GSR_PBWD_NT 1
-#endif
 typedef float pbwd_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void wave_store_rows(float* __restrict__ g, const float* __restrict__ l, int nf, int lane) {
     const int n4 = nf >> 2;
     for (int c = lane; c < n4; c += 64) {
-        if constexpr (GSR_PBWD_NT)
-            __builtin_nontemporal_store(reinterpret_cast<const pbwd_f4*>(l)[c], reinterpret_cast<pbwd_f4*>(g) + c);
-        else
-            reinterpret_cast<float4*>(g)[c] = reinterpret_cast<const float4*>(l)[c];
+        __builtin_nontemporal_store(reinterpret_cast<const pbwd_f4*>(l)[c], reinterpret_cast<pbwd_f4*>(g) + c);
     }
     for (int c = (n4 << 2) + lane; c < nf; c += 64) g[c] = l[c];
 }
 
-#ifndef GSR_PBWD_WAVES
-#define GSR_PBWD_WAVES 0
-#endif
 #ifndef GSR_PBWD_STAGE_WAVES
 #define GSR_PBWD_STAGE_WAVES 3
-#endif
-#ifndef GSR_PBWD_STAGE_DEFAULT
-#define GSR_PBWD_STAGE_DEFAULT 1  // staged row stores: C5 preprocess_bwd 1.18-1.22 -> 0.91-0.93 ms, C3 0.151 -> 0.122
 #endif
 // STAGE (SH rows of 16 coefficients, launch ranges in whole workgroups): the
 // SH and SG-7 gradient rows go out through LDS as whole-wave stores (and the
 // SG-7 input rows come in by 16-B LDS-DMA).  Every lane of a wave then takes
 // part, so a lane past the range computes the wave's first Gaussian (`wbase`)
 // again (same values to the same addresses) and only its staged rows are left out.
-template <bool STAGE>
-#if GSR_PBWD_WAVES
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSR_PBWD_WAVES, 8)))
-preprocess_bwd_kernel(PreprocessBwdArgs a) {
-#else
 // (STAGE: the lobe rows live in LDS, not VGPRs: 3 waves per SIMD fit (168 VGPRs, 6 spilled); LDS 49 KB
 // per block, 3 blocks per CU)
+template <bool STAGE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(STAGE ? GSR_PBWD_STAGE_WAVES : 1, 8)))
 preprocess_bwd_kernel(PreprocessBwdArgs a) {
-#endif
     const int idx0 = a.begin + blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int wbase = idx0 - lane;  // the wave's first Gaussian
@@ -289,7 +269,6 @@ preprocess_bwd_kernel(PreprocessBwdArgs a) {
         q_in[2] = q4.z;
         q_in[3] = q4.w;
     }
-#if GSR_SG_UNROLL
     // (SG degree 7: the 196-B lobe rows as well; 2 waves per SIMD fit them)
     const bool sg7 = a.shs && a.SGM == kSG7 && a.SGD == kSG7;
     SG7Rows sgr;
@@ -302,7 +281,6 @@ preprocess_bwd_kernel(PreprocessBwdArgs a) {
     } else if (sg7) {
         sg7_load(a, idx, sgr);
     }
-#endif
     // extension outputs straight from the accumulator (zero for culled
     // Gaussians); sample_depth returns neither (rasterize_points.cu:633)
     if (a.dL_dmean2D) {
@@ -679,7 +657,6 @@ preprocess_bwd_kernel(PreprocessBwdArgs a) {
         float ddx = gdx[0] * dR0 + gdx[1] * dR1 + gdx[2] * dR2;
         float ddy = gdy[0] * dR0 + gdy[1] * dR1 + gdy[2] * dR2;
         float ddz = gdz[0] * dR0 + gdz[1] * dR1 + gdz[2] * dR2;
-#if GSR_SG_UNROLL
         if (sg7) {
             if constexpr (STAGE) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA row loads have landed
@@ -687,39 +664,39 @@ preprocess_bwd_kernel(PreprocessBwdArgs a) {
             } else {
                 sg7_bwd(a, idx, sgr, x, y, z, dR0, dR1, dR2, ddx, ddy, ddz);
             }
-        } else
-#endif
-        for (int sg = 0; sg < a.SGM; sg++) {
-            const size_t o = (size_t)idx * a.SGM + sg;
-            if (sg >= a.SGD) {
-                if (a.dc_rows) continue;
-                a.dL_dsg_sharpness[o] = 0.f;
-                for (int c = 0; c < 3; c++) {
-                    a.dL_dsg_axis[3 * o + c] = 0.f;
-                    a.dL_dsg_color[3 * o + c] = 0.f;
+        } else {
+            for (int sg = 0; sg < a.SGM; sg++) {
+                const size_t o = (size_t)idx * a.SGM + sg;
+                if (sg >= a.SGD) {
+                    if (a.dc_rows) continue;
+                    a.dL_dsg_sharpness[o] = 0.f;
+                    for (int c = 0; c < 3; c++) {
+                        a.dL_dsg_axis[3 * o + c] = 0.f;
+                        a.dL_dsg_color[3 * o + c] = 0.f;
+                    }
+                    continue;
                 }
-                continue;
+                const float* ax = a.sg_axis + 3 * o;
+                const float* gc = a.sg_color + 3 * o;
+                const float sharp = a.sg_sharpness[o];
+                const float auxs = (ax[0] * x + ax[1] * y + ax[2] * z) - 1.0f;
+                const float gs = expf(sharp * auxs);
+                const float dL_dgs = gc[0] * dR0 + gc[1] * dR1 + gc[2] * dR2;
+                const float dL_dexp = dL_dgs * gs;
+                const float dL_daux = dL_dexp * sharp;
+                if (!a.dc_rows) {
+                    a.dL_dsg_color[3 * o + 0] = dR0 * gs;
+                    a.dL_dsg_color[3 * o + 1] = dR1 * gs;
+                    a.dL_dsg_color[3 * o + 2] = dR2 * gs;
+                    a.dL_dsg_sharpness[o] = dL_dexp * auxs;
+                    a.dL_dsg_axis[3 * o + 0] = dL_daux * x;
+                    a.dL_dsg_axis[3 * o + 1] = dL_daux * y;
+                    a.dL_dsg_axis[3 * o + 2] = dL_daux * z;
+                }
+                ddx += dL_daux * ax[0];
+                ddy += dL_daux * ax[1];
+                ddz += dL_daux * ax[2];
             }
-            const float* ax = a.sg_axis + 3 * o;
-            const float* gc = a.sg_color + 3 * o;
-            const float sharp = a.sg_sharpness[o];
-            const float auxs = (ax[0] * x + ax[1] * y + ax[2] * z) - 1.0f;
-            const float gs = expf(sharp * auxs);
-            const float dL_dgs = gc[0] * dR0 + gc[1] * dR1 + gc[2] * dR2;
-            const float dL_dexp = dL_dgs * gs;
-            const float dL_daux = dL_dexp * sharp;
-            if (!a.dc_rows) {
-                a.dL_dsg_color[3 * o + 0] = dR0 * gs;
-                a.dL_dsg_color[3 * o + 1] = dR1 * gs;
-                a.dL_dsg_color[3 * o + 2] = dR2 * gs;
-                a.dL_dsg_sharpness[o] = dL_dexp * auxs;
-                a.dL_dsg_axis[3 * o + 0] = dL_daux * x;
-                a.dL_dsg_axis[3 * o + 1] = dL_daux * y;
-                a.dL_dsg_axis[3 * o + 2] = dL_daux * z;
-            }
-            ddx += dL_daux * ax[0];
-            ddy += dL_daux * ax[1];
-            ddz += dL_daux * ax[2];
         }
         // dnormvdv (auxiliary.h:104-113)
         const float inv = 1.0f / dlen;
@@ -852,7 +829,8 @@ hipError_t launch_preprocess_bwd(const BwdParams& b, const GeomState& gs, const 
     a.end = end;
     a.dc_rows = dc_rows;
     // staged row stores: the 16-coefficient SH layout, 16-B aligned rows, SG degree 0 or 7 (the
-    // configurations with wide rows), whole-workgroup ranges; GSR_OPT_PBWD_STAGE 1 forces it, 2 turns it off.
+    // configurations with wide rows), whole-workgroup ranges; GSR_OPT_PBWD_STAGE 0 (the default) and 1 take it,
+    // 2 turns it off (C5 preprocess_bwd 1.18-1.22 -> 0.91-0.93 ms staged, C3 0.151 -> 0.122).
     // Alignment of every row base the stage touches: the gradient rows it stores and, at SG 7, the lobe
     // input rows it loads by 16-B LDS-DMA (a tensor that is a view at a 4-B offset takes the per-lane path)
     const int so = option(kOptPbwdStage);
@@ -861,7 +839,7 @@ hipError_t launch_preprocess_bwd(const BwdParams& b, const GeomState& gs, const 
                           (p.SGM == 0 || (p.SGM == kSG7 && p.SGD == kSG7 && al16(b.dL_dsg_color) &&
                                           al16(b.dL_dsg_sharpness) && al16(b.dL_dsg_axis) &&
                                           al16(p.sg_color) && al16(p.sg_sharpness) && al16(p.sg_axis)));
-    const bool stage = stage_ok && (so == 1 || (so == 0 && GSR_PBWD_STAGE_DEFAULT));
+    const bool stage = stage_ok && (so == 0 || so == 1);
     if (stage)
         hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((end - begin + 255) / 256), dim3(256), 0, stream, a);
     else

@@ -26,15 +26,8 @@
 // with the records restaged per pass.
 // Contraction is off for this file: every fma below is written out, so each
 // template instance (plain, GSR_OPT_RENDER_STATS, the sample queries) rounds
-// identically.
-#ifndef GSR_FWD_CONTRACT
-#define GSR_FWD_CONTRACT 0  // (development: 1 = contract(fast) outside the shared footprint helpers)
-#endif
-#if GSR_FWD_CONTRACT
-#pragma clang fp contract(fast)
-#else
+// identically (contract(fast) outside the shared footprint helpers: measured and not adopted).
 #pragma clang fp contract(off)
-#endif
 
 #include <type_traits>
 
@@ -43,30 +36,62 @@
 #include "gsr_kernels.h"
 #include "tiles.h"
 
-namespace gsr {
-
+// The build switches of this file (-D; DESIGN.md lists every switch the library keeps).
+// Launch geometry:
 #ifndef GSR_RESIDENT
-#define GSR_RESIDENT 256
+#define GSR_RESIDENT 256  // records of the LDS-resident contributing prefix
 #endif
 #ifndef GSR_BATCH
-#define GSR_BATCH 128
+#define GSR_BATCH 128  // records per composite staging batch
 #endif
+#ifndef GSR_FWD_WAVES
+#define GSR_FWD_WAVES 6  // waves per SIMD the kernel is compiled for (a GSR_DBG_ROOT trace build needs 5)
+#endif
+#ifndef GSR_SAMPLE_WAVES
+#define GSR_SAMPLE_WAVES 7  // the same for the SAMPLE instance (72 VGPRs; the grouped exact dT/dt_m walk took it to 74 = 6 waves)
+#endif
+// Instrumentation (development builds):
+#ifndef GSR_PHASE_CLOCK
+#define GSR_PHASE_CLOCK 0  // STATS instances: shader clocks at the phase boundaries in render stats [8..15]
+#endif
+#ifndef GSR_LEFT_STATS
+#define GSR_LEFT_STATS 0  // render stats slots 12..15 count why pixels are left to the passes
+#endif
+#ifndef GSR_TIME_COMPOSITE_ONLY
+#define GSR_TIME_COMPOSITE_ONLY 0  // timing build: skip the median depth, its outputs are then wrong
+#endif
+#ifndef GSR_TIME_SAMPLE_COMPOSITE_ONLY
+#define GSR_TIME_SAMPLE_COMPOSITE_ONLY 0  // timing build: the SAMPLE raster without its median depth
+#endif
+#ifndef GSR_SAMPLE_PROLOGUE_ONLY
+#define GSR_SAMPLE_PROLOGUE_ONLY 0  // timing build: the SAMPLE raster's prologue alone; its outputs are wrong
+#endif
+// -DGSR_DBG_PX=x -DGSR_DBG_PY=y prints the median-depth phases' results for one pixel; with -DGSR_DBG_ROOT
+// also every root_update of that pixel (or of GSR_DBG_ROOT_PX, GSR_DBG_ROOT_PY); -DGSR_DBG_DT prints the
+// refined roots published with a non-negative dT/dt_m.
+#ifdef GSR_DBG_PX
+#define GSR_DBG(p, ...) \
+    do { if (x0 + ((p) & 15) == GSR_DBG_PX && y0 + ((p) >> 4) == GSR_DBG_PY) printf(__VA_ARGS__); } while (0)
+#define GSR_DBG_NEAR(p, ...) \
+    do { if (abs(x0 + ((p) & 15) - GSR_DBG_PX) <= 1 && abs(y0 + ((p) >> 4) - GSR_DBG_PY) <= 1) printf(__VA_ARGS__); } while (0)
+#else
+#define GSR_DBG(p, ...) do { } while (0)
+#define GSR_DBG_NEAR(p, ...) do { } while (0)
+#endif
+#if defined(GSR_DBG_ROOT) && !defined(GSR_DBG_ROOT_PX)
+#define GSR_DBG_ROOT_PX GSR_DBG_PX
+#define GSR_DBG_ROOT_PY GSR_DBG_PY
+#endif
+
+namespace gsr {
+
 constexpr int kResident = GSR_RESIDENT;  // LDS-resident contributing prefix (C3: every tile's max contributor <= 184)
 constexpr int kMaskWords = kResident / 32;
 constexpr int kBatch = GSR_BATCH;        // records per composite staging batch
-// The median-depth walks take a step's two contributors' fields in the halves of packed register pairs.
-// GSR_WALK_SOA = 1: the staged records are 12 SoA planes of kPlane floats and a field pair is two
-// ds_read_b32 straight into the pair's halves (no moves; kPlane = kResident + 1 keeps the compiler from
-// merging two fields of one record into a ds_read2); 0: the float4 records (three ds_read_b128 each) and
-// the pairs built by moves.
-#ifndef GSR_WALK_SOA
-#define GSR_WALK_SOA 1
-#endif
-constexpr bool kWalkSoA = GSR_WALK_SOA;
-#ifndef GSR_SAMPLE_WALK_SOA
-#define GSR_SAMPLE_WALK_SOA GSR_WALK_SOA  // (the SAMPLE instance's own choice: A/B)
-#endif
-constexpr bool kSampleWalkSoA = GSR_SAMPLE_WALK_SOA;
+// The median-depth walks take a step's two contributors' fields in the halves of packed register pairs:
+// the staged records are 12 SoA planes of kPlane floats and a field pair is two ds_read_b32 straight into
+// the pair's halves (no moves; kPlane = kResident + 1 keeps the compiler from merging two fields of one
+// record into a ds_read2).  (The float4 records with the pairs built by moves: rejected, DESIGN.md.)
 constexpr int kPlane = kResident + 1;
 constexpr int kPlanes = 12;  // x, y, conic a, b, c, opacity, plane x, y, |t|, rsigma, sc, ball
 constexpr int kRecSlots = 3 * kPlane > 4 * kBatch ? 3 * kPlane : 4 * kBatch;
@@ -133,8 +158,6 @@ struct RenderFwdArgs {
 //  * a non-ball splat (rsigma <= 0, g = 0 in the reference) runs with
 //    alpha_g = 0 and sc = 0: u = 0, g = 1, 1 - 0*g = 1 exactly.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 ld4(const float4* p) { return *reinterpret_cast<const f32x4*>(p); }
 constexpr float kSqrtHalfLog2e = 0.84932180028801904272f;  // sqrt(0.5 log2 e)
 constexpr float kLog2e = 1.44269504088896340736f;          // (__expf(x) = v_exp_f32(x * kLog2e))
 
@@ -191,7 +214,7 @@ __device__ __forceinline__ void bisect_step(f32x2 (&A)[NP], f32x2 (&B)[NP], cons
 //     Halley iterate after it is then ~(step / sigma)^2 closer still), and
 //     keeps the result where the root is well conditioned (|H'| kCondTol
 //     max(t, 1) >= kHNoise).
-// Lanes not done after kRefineWalks walks and ill-conditioned lanes run the
+// Lanes not done after their phase's walks and ill-conditioned lanes run the
 // reference's 5 passes from its first window (the root of a T that stays
 // within rounding of 1/2 over a stretch is decided by rounding: there only
 // the reference's own sample grid reproduces its answer).  Measured on C3
@@ -199,54 +222,20 @@ __device__ __forceinline__ void bisect_step(f32x2 (&A)[NP], f32x2 (&B)[NP], cons
 // (the slowest lane), max |refined - bisected| = 2.4e-7, no lane left to the
 // passes.  (The previous scheme ran the reference's first two passes and
 // refined from the pass-2 cell: one more 7-sample walk per contributor.)
-#ifndef GSR_PROBES
-#define GSR_PROBES 7  // (11 -> 9 -> 7: render_fwd 0.769 -> 0.758 -> (later build) 0.683 -> 0.671 ms at C3, profiles/r4_ab_probes.txt)
-#endif
-constexpr int kProbes = GSR_PROBES;  // 11 (the window ends, m0 and 8 offsets around it); 9 or 7 (no ends)
-// With 9 probes the window ends are not sampled: T is non-increasing in t, so a bracket between the
-// inner probes (m0 -/+ SAMPLE_RANGE / 2) implies the reference's in_range test (T(e0) >= 1/2 >= T(e8));
+// (11 -> 9 -> 7 probes: render_fwd 0.769 -> 0.758 -> (later build) 0.683 -> 0.671 ms at C3, profiles/r4_ab_probes.txt)
+constexpr int kProbes = 7;  // m0 and 6 offsets around it
+// The window ends are not sampled: T is non-increasing in t, so a bracket between the outer probes
+// (m0 -/+ SAMPLE_RANGE / 4) implies the reference's in_range test (T(e0) >= 1/2 >= T(e8));
 // a pixel whose root lies outside them is left to the reference's passes.
-constexpr bool kProbeEnds = kProbes == 11;
-#if GSR_PROBES == 7
 __constant__ constexpr float kProbeOffsets[kProbes] = {-0.25f, -0.125f, -0.0625f, 0.f, 0.0625f, 0.125f, 0.25f};
-#elif GSR_PROBES == 9
-__constant__ constexpr float kProbeOffsets[kProbes] = {-0.5f, -0.25f, -0.125f, -0.0625f, 0.f,
-                                                        0.0625f, 0.125f, 0.25f, 0.5f};
-#else
-__constant__ constexpr float kProbeOffsets[kProbes] = {0.f,    -0.5f,   -0.25f, -0.125f, -0.0625f, 0.f,
-                                                        0.0625f, 0.125f, 0.25f,  0.5f,    0.f};
-#endif
 constexpr uint32_t kPubRefined = 1u, kPubOut = 2u, kPubIll = 4u;  // phase results: root found / not in range /
                                                                    // root found, ill-conditioned (below)
 constexpr uint32_t kPubBracket = 128u;  // left to the passes with an evaluated bracket [lo, hi] of the root
 constexpr uint32_t kLastMask = 0x3fffffffu, kLoEv = 1u << 30, kHiEv = 1u << 31;  // (s_pub_last of a phase-2b pixel)
-#ifndef GSR_REFINE_WALKS
-#define GSR_REFINE_WALKS 4
-#endif
-constexpr int kRefineWalks = GSR_REFINE_WALKS;
-// SAMPLE mode: Halley walks from the query point's own distance (GSR_SAMPLE_GUESS, in the kernel)
-#ifndef GSR_SAMPLE_GUESS
-#define GSR_SAMPLE_GUESS 1
-#endif
-#ifndef GSR_SAMPLE_WALKS
-#define GSR_SAMPLE_WALKS 5
-#endif
-constexpr int kSampleWalks = GSR_SAMPLE_WALKS;
-#ifndef GSR_SAMPLE_DT_TOL
-#define GSR_SAMPLE_DT_TOL 0.004f  // (SAMPLE) longest step, relative to the curvature length, dT/dt_m is continued over
-#endif
-constexpr float kSampleDtTol = GSR_SAMPLE_DT_TOL;
-#ifndef GSR_SAMPLE_PASS_GROUP
-#define GSR_SAMPLE_PASS_GROUP 1  // (SAMPLE) the passes and the exact dT/dt_m walk of left points in lane groups
-#endif
-#ifndef GSR_SAMPLE_NO_ENDS
-#define GSR_SAMPLE_NO_ENDS 1  // (round 5: sample_fwd 0.839-0.844 -> 0.792-0.812 ms at the sample bench; 2 more of 1.27M points to the passes)
-#endif
-constexpr bool kSampleNoEnds = GSR_SAMPLE_NO_ENDS;
-#ifndef GSR_REFINE_TOL
-#define GSR_REFINE_TOL 3e-5f
-#endif
-constexpr float kRefineTol = GSR_REFINE_TOL;
+// SAMPLE mode: Halley walks from the query point's own distance (in the kernel)
+constexpr int kSampleWalks = 5;
+constexpr float kSampleDtTol = 0.004f;  // (SAMPLE) longest step, relative to the curvature length, dT/dt_m is continued over
+constexpr float kRefineTol = 3e-5f;
 // A longer Newton step is accepted too when it is short against the local
 // curvature length of H: |H / H'| <= kLooseTol max(t, 1) and |H / H'| F / |H'|
 // <= kCurvTol, F = sum |H'' terms| (bounds H'' across the splat peaks where it
@@ -255,22 +244,10 @@ constexpr float kRefineTol = GSR_REFINE_TOL;
 // (tools/sim/s4_sim.py, SIM_LOOSE / SIM_TOLF: on C3 phase-2 second walks
 // 11.2k -> 3.9k of 50.8k lanes, phase-1 wave walks 2.41 -> 2.14, max
 // |refined - bisected| 2.4e-7 -> 9.5e-7).
-#ifndef GSR_LOOSE_TOL
-#define GSR_LOOSE_TOL 2e-4f
-#endif
-#ifndef GSR_CURV_TOL
-#define GSR_CURV_TOL 0.02f
-#endif
-constexpr float kLooseTol = GSR_LOOSE_TOL;
-constexpr float kCurvTol = GSR_CURV_TOL;
+constexpr float kLooseTol = 2e-4f;
+constexpr float kCurvTol = 0.02f;
 constexpr float kCondTol = 1e-6f;   // conditioning threshold (as the previous scheme's tolerance)
 constexpr float kTwoLn2 = 1.38629436111989061883f;
-#ifndef GSR_ILL_NEWTON
-#define GSR_ILL_NEWTON 1
-#endif
-#ifndef GSR_HNOISE
-#define GSR_HNOISE 1e-5f
-#endif
 // A converged root whose noise-induced uncertainty kHNoise / |H'| is above the
 // kCondTol bar but below kIllTol max(t, 1) (T flat near 1/2 between two
 // splats' peaks: C2 leaves 98k of 640k pixels so) is kept as the median depth
@@ -279,36 +256,15 @@ constexpr float kTwoLn2 = 1.38629436111989061883f;
 // depth in one more walk — instead of the reference's five passes plus that
 // walk.  (The continued H'' value refined lanes use would be off by ~kCurvTol^2
 // relative, which the implicit gradient's 1 / dT/dt_m amplifies at such pixels.)
-#ifndef GSR_ILL_ACCEPT
-#define GSR_ILL_ACCEPT 1
-#endif
 constexpr float kIllTol = 1e-5f;
-constexpr float kHNoise = GSR_HNOISE;  // rounding noise assumed in log2 T (~10x a 64-factor product's; 2e-6 measured: C2 render_fwd 0.763 -> 0.717 ms, but a small scene's dL/dmeans2D drifts to 1.3e-4 of the oracle through the implicit median-depth gradient)
+constexpr float kHNoise = 1e-5f;  // rounding noise assumed in log2 T (~10x a 64-factor product's; 2e-6 measured: C2 render_fwd 0.763 -> 0.717 ms, but a small scene's dL/dmeans2D drifts to 1.3e-4 of the oracle through the implicit median-depth gradient)
 
-__device__ __forceinline__ void refine_step(float& A, float& B, float& D, float& E, float& F, float t, float alpha,
-                                            float t_peak, float sc, float bm) {
-    const float om = 1.f - alpha;
-    const float u = __builtin_fmaf(t, sc, -t_peak * sc);
-    const float u2 = u * u;
-    const float ag = (alpha * bm) * __builtin_amdgcn_exp2f(-u2);
-    const float omg = 1.f - ag;
-    const bool behind = t > t_peak;
-    A *= behind ? om : omg;
-    B *= omg;
-    const float x = ag * __builtin_amdgcn_rcpf(omg);
-    const float xs = x * sc;
-    D = __builtin_fmaf(xs, fabsf(u), D);
-    const float xsc = xs * sc;
-    const float p = __builtin_fmaf(-kTwoLn2 * u2, 1.f + x, 1.f);
-    E = __builtin_fmaf(behind ? -xsc : xsc, p, E);
-    F = __builtin_fmaf(xsc, fabsf(p), F);  // bounds |H''| on either side of every splat peak (where H'' jumps)
-}
-
-// refine_step for the walk's two contributors at once, in the halves of packed registers: every product
+// One contributor's terms of the products A, B and the sums D = -H', E = H'', F (above) at depth t, for the
+// walk's two contributors at once in the halves of packed registers: every product
 // and sum chain is kept per half (A, B, D, E, F pairs, combined after the walk), so the two chains are
 // independent and each op is one v_pk_* instruction; the transcendentals, compares and selects stay
-// per half.  Same per-contributor arithmetic as refine_step (a lone contributor's partner has alpha = 0:
-// factors exactly 1, terms exactly 0).
+// per half (a lone contributor's partner has alpha = 0: factors exactly 1, terms exactly 0).
+// F = sum xsc |p| bounds |H''| on either side of every splat peak (where H'' jumps).
 __device__ __forceinline__ void refine_step2(f32x2& A, f32x2& B, f32x2& D, f32x2& E, f32x2& F, f32x2 t2,
                                              f32x2 alpha, f32x2 t_peak, f32x2 sc, f32x2 bm) {
     const f32x2 one = {1.f, 1.f};
@@ -385,60 +341,22 @@ __device__ unsigned long long g_render_stats[kRenderStats];
 // blocks per CU) 0.893; a 192-record cache 0.820; 64-record batches 0.825.
 // Tiles whose contributing prefix exceeds the cache take the wave-uniform
 // walk (C3's largest per-tile max contributor is 184).
-// Development: -DGSR_DBG_PX=x -DGSR_DBG_PY=y prints the median-depth phases' results for one pixel.
-#ifdef GSR_DBG_PX
-#define GSR_DBG(p, ...) \
-    do { if (x0 + ((p) & 15) == GSR_DBG_PX && y0 + ((p) >> 4) == GSR_DBG_PY) printf(__VA_ARGS__); } while (0)
-#define GSR_DBG_NEAR(p, ...) \
-    do { if (abs(x0 + ((p) & 15) - GSR_DBG_PX) <= 1 && abs(y0 + ((p) >> 4) - GSR_DBG_PY) <= 1) printf(__VA_ARGS__); } while (0)
-#else
-#define GSR_DBG(p, ...) do { } while (0)
-#define GSR_DBG_NEAR(p, ...) do { } while (0)
-#endif
-#ifndef GSR_FWD_WAVES
-#define GSR_FWD_WAVES 6
-#endif
-#ifndef GSR_SAMPLE_WAVES
-#define GSR_SAMPLE_WAVES 7  // (the SAMPLE instance: 72 VGPRs; the grouped exact dT/dt_m walk took it to 74 = 6 waves)
-#endif
 
 // Median-depth phases 2b and 3 (render path) give each listed pixel as many
 // lanes as one round of the block allows (up to 16), instead of 4 and 1.
-#ifndef GSR_ADAPT_GROUPS
-#define GSR_ADAPT_GROUPS 1
-#endif
-constexpr bool kAdaptGroups = GSR_ADAPT_GROUPS;
-// Phase 2 without the window-end samples (in_range implied by a root well inside the window).
-#ifndef GSR_P2_NOENDS
-#define GSR_P2_NOENDS 1  // (0: ends sampled in the first walk; render_fwd 0.738 -> 0.682 ms at C3 with 1, profiles/r4_ab_p2_noends.txt)
-#endif
-constexpr bool kP2NoEnds = GSR_P2_NOENDS;
-// Phase 1 with one Halley walk: a grid pixel that needs more continues in phase 2 on its own lane
-// (whose fourth wave was idle) from its iterate, which its neighbours take as their guess.
-#ifndef GSR_P1_ONE
-#define GSR_P1_ONE 1  // (0: up to 4 Halley walks in phase 1; render_fwd 0.672 -> 0.628 ms at C3 with 1, profiles/r4_ab_p1_one.txt)
-#endif
-constexpr bool kP1One = GSR_P1_ONE;
+// Phase 2 runs without the window-end samples (in_range implied by a root well inside the window;
+// ends sampled in the first walk: render_fwd 0.682 -> 0.738 ms at C3, profiles/r4_ab_p2_noends.txt).
+// Phase 1 runs one Halley walk: a grid pixel that needs more continues in phase 2 on its own lane
+// (whose fourth wave was idle) from its iterate, which its neighbours take as their guess
+// (up to 4 Halley walks in phase 1: render_fwd 0.628 -> 0.672 ms at C3, profiles/r4_ab_p1_one.txt).
 // Phase 2b: Halley walks of a straggler before it is left to the passes (3: C2 render_fwd 0.500 -> 0.490 ms,
-// C3 unchanged, profiles/r4_ab_p2b_walks.txt; the sample path keeps kRefineWalks)
-#ifndef GSR_P2B_WALKS
-#define GSR_P2B_WALKS 2
-#endif
-constexpr int kP2bWalks = GSR_P2B_WALKS;
-#ifndef GSR_P3_ILL_SHIFT
-#define GSR_P3_ILL_SHIFT 3  // phase 3: an ill-conditioned root's group is at least G_p >> this (2 and 4: the same within noise, profiles/r4_ab_p3_ill_floor.txt)
-#endif
-#ifndef GSR_PASS_SKIP
-#define GSR_PASS_SKIP 1  // phase 3 skips the reference passes a pixel's evaluated bracket decides
-#endif
-#ifndef GSR_LEFT_STATS
-#define GSR_LEFT_STATS 0  // (development: render stats slots 12..15 count why pixels are left to the passes)
-#endif
-// Phase 2b group size: the largest (at most 16 lanes) that runs every straggler in one round, down to
-// GSR_P2B_ONE_ROUND - 1 as log2 (0: 16 / 8 / 4 lanes by count, more rounds above 64 stragglers)
-#ifndef GSR_P2B_ONE_ROUND
-#define GSR_P2B_ONE_ROUND 1  // (C2 render_fwd 0.523 -> 0.503 ms, C3 unchanged; profiles/r4_ab_p2b_one_round.txt)
-#endif
+// C3 unchanged, profiles/r4_ab_p2b_walks.txt)
+constexpr int kP2bWalks = 2;
+// phase 3: an ill-conditioned root's group is at least G_p >> this (2 and 4: the same within noise, profiles/r4_ab_p3_ill_floor.txt)
+constexpr int kP3IllShift = 3;
+// Phase 2b group size: the largest (at most 16 lanes) that runs every straggler in one round
+// (16 / 8 / 4 lanes by count, more rounds above 64 stragglers: C2 render_fwd 0.503 -> 0.523 ms, C3 unchanged;
+// profiles/r4_ab_p2b_one_round.txt)
 
 template <bool GEOM, bool STATS = false, bool SAMPLE = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPLE && GEOM && !STATS) ? GSR_SAMPLE_WAVES : GSR_FWD_WAVES, 8))) render_fwd_kernel(RenderFwdArgs a) {
@@ -457,16 +375,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
     __shared__ uint32_t s_pub_last[kPub];
     __shared__ float s_pub_m0[kPub], s_pub_T[kPub];
     __shared__ float s_groot[(GEOM && !SAMPLE) ? 64 : 1];  // then the compacted phase-2 list (bytes)
-    __shared__ uint8_t s_glive[(GEOM && !SAMPLE) ? 64 : 1];  // (kP1One) grid pixel continued in phase 2
+    __shared__ uint8_t s_glive[(GEOM && !SAMPLE) ? 64 : 1];  // grid pixel continued in phase 2
     __shared__ float s_pub_hi[kPub];
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     // (development, STATS builds with -DGSR_PHASE_CLOCK=1: shader clocks at the render path's phase
     // boundaries, summed per wave into render stats [8..13] in place of the per-phase walk counts)
-#ifndef GSR_PHASE_CLOCK
-#define GSR_PHASE_CLOCK 0
-#endif
     constexpr bool kClock = GSR_PHASE_CLOCK && STATS;
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto stamp = [&](int k) {
@@ -488,16 +403,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
         const float2 xy = inside ? a.pt_xy[pid] : make_float2(0.f, 0.f);
         pixx = xy.x;
         pixy = xy.y;
-        pt_t = inside ? a.pt_t[pid] : 0.f;  // (GEOM: the refinement's start, GSR_SAMPLE_GUESS)
-#ifndef GSR_SAMPLE_SORT
-#define GSR_SAMPLE_SORT 1
-#endif
-        if constexpr (GEOM && GSR_SAMPLE_SORT) {
+        pt_t = inside ? a.pt_t[pid] : 0.f;  // (GEOM: the refinement's start)
+        if constexpr (GEOM) {
             // The chunk's points reordered by their pixel cell in the tile (row-major 16 x 16), so each wave
             // holds a compact patch of the tile as the render path's 16 x 4 strips: neighbouring points
             // blend similar sets, which makes a wave's composite and walks less divergent (the scatter into
             // the tile ranges leaves the points in arbitrary order).  A counting sort in LDS, before any
-            // staging uses it; no output depends on which lane works a point.
+            // staging uses it; no output depends on which lane works a point.  (Unsorted chunks: DESIGN.md.)
             uint32_t* s_cnt = reinterpret_cast<uint32_t*>(s_rec);  // [256] counts, then offsets
             uint32_t* s_sp = s_cnt + kTilePixels;                  // [256] point id, x, y, |p_view| by rank
             float* s_sx = reinterpret_cast<float*>(s_sp + kTilePixels);
@@ -761,12 +673,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
     auto lane_mask = [&]() -> const uint32_t* { return s_mask + (GEOM ? opaque_int(tid) : 0); };
     float mDepth = 0.f, md_out = 0.f, md_dT = 0.f;
     bool md_ok = false, md_in_range = false;
-#ifndef GSR_TIME_COMPOSITE_ONLY
-#define GSR_TIME_COMPOSITE_ONLY 0  // (timing builds only: skip the median depth, its outputs are then wrong)
-#endif
-#ifndef GSR_TIME_SAMPLE_COMPOSITE_ONLY
-#define GSR_TIME_SAMPLE_COMPOSITE_ONLY 0  // (timing builds only: the SAMPLE raster without its median depth)
-#endif
     if constexpr (GEOM && !(GSR_TIME_COMPOSITE_ONLY && !SAMPLE) && !(GSR_TIME_SAMPLE_COMPOSITE_ONLY && SAMPLE)) {
         unsigned long long st[kRenderStats] = {0, 0, cst[0], cst[1]};
         int st_phase = 0;  // (STATS) render-path phase of the walks below
@@ -778,24 +684,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
         float dmin = 0.f, dmax = 0.f;
         bool in_range = T <= kMinTransmittance;
         const bool resident = max_contrib <= (uint32_t)kResident;
-        float4* c_w0 = s_rec;
-        float4* c_w1 = s_rec + kResident;
-        float4* c_w2 = s_rec + 2 * kResident;
-        constexpr bool kSoA = SAMPLE ? kSampleWalkSoA : kWalkSoA;
-        float* const s_pl = reinterpret_cast<float*>(s_rec);  // (kSoA) kPlanes planes of kPlane floats
+        float* const s_pl = reinterpret_cast<float*>(s_rec);  // kPlanes planes of kPlane floats
         auto pl = [&](int f, int j) -> float { return s_pl[f * kPlane + j]; };
         auto pl2 = [&](int f, int j1, int j2) -> f32x2 { return f32x2{s_pl[f * kPlane + j1], s_pl[f * kPlane + j2]}; };
         // one staged record as the three float4 words (w2 = |t|, rsigma, sc, ball)
         auto rec = [&](int j, float4& w0, float4& w1, float4& w2) {
-            if constexpr (kSoA) {
-                w0 = make_float4(pl(0, j), pl(1, j), pl(2, j), pl(3, j));
-                w1 = make_float4(pl(4, j), pl(5, j), pl(6, j), pl(7, j));
-                w2 = make_float4(pl(8, j), pl(9, j), pl(10, j), pl(11, j));
-            } else {
-                w0 = c_w0[j];
-                w1 = c_w1[j];
-                w2 = c_w2[j];
-            }
+            w0 = make_float4(pl(0, j), pl(1, j), pl(2, j), pl(3, j));
+            w1 = make_float4(pl(4, j), pl(5, j), pl(6, j), pl(7, j));
+            w2 = make_float4(pl(8, j), pl(9, j), pl(10, j), pl(11, j));
         };
         const int chunk = resident ? kResident : kTilePixels;
         const int chunks = ((int)max_contrib + chunk - 1) / chunk;
@@ -805,15 +701,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 const float4 w0 = sp->w0, w1 = sp->w1, w2s = sp->w2;
                 const bool ball = w2s.y > 0.f;  // non-ball splats: g = 0 (bisect_step)
                 const float4 w2 = make_float4(w2s.x, w2s.y, ball ? w2s.y * kSqrtHalfLog2e : 0.f, ball ? 1.f : 0.f);
-                if constexpr (kSoA) {
-                    const float v[kPlanes] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
+                const float v[kPlanes] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w};
 #pragma unroll
-                    for (int f = 0; f < kPlanes; f++) s_pl[f * kPlane + k] = v[f];
-                } else {
-                    c_w0[k] = w0;
-                    c_w1[k] = w1;
-                    c_w2[k] = w2;
-                }
+                for (int f = 0; f < kPlanes; f++) s_pl[f * kPlane + k] = v[f];
             }
         };
         if (resident && max_contrib > 0) {
@@ -859,22 +749,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 // both contributors' footprint in packed halves, with splat_power / splat_tpeak's
                 // roundings (packed fp32 rounds as the scalar ops: alpha stays bit-identical to the
                 // composite's and the backward's); __expf(x) = v_exp_f32(x log2 e)
-                f32x2 X, Y, CA, CB, CC, OP, PX, PY, TT, RS, SC, BM;
-                if constexpr (kSoA) {
-                    X = pl2(0, j1, j2), Y = pl2(1, j1, j2), CA = pl2(2, j1, j2), CB = pl2(3, j1, j2);
-                    CC = pl2(4, j1, j2), OP = pl2(5, j1, j2), PX = pl2(6, j1, j2), PY = pl2(7, j1, j2);
-                    TT = pl2(8, j1, j2), RS = pl2(9, j1, j2), SC = pl2(10, j1, j2), BM = pl2(11, j1, j2);
-                } else {
-                    const f32x4 a0 = ld4(c_w0 + j1), b0 = ld4(c_w0 + j2);
-                    const f32x4 a1 = ld4(c_w1 + j1), b1 = ld4(c_w1 + j2);
-                    const f32x4 a2 = ld4(c_w2 + j1), b2 = ld4(c_w2 + j2);
-                    X = __builtin_shufflevector(a0, b0, 0, 4), Y = __builtin_shufflevector(a0, b0, 1, 5);
-                    CA = __builtin_shufflevector(a0, b0, 2, 6), CB = __builtin_shufflevector(a0, b0, 3, 7);
-                    CC = __builtin_shufflevector(a1, b1, 0, 4), OP = __builtin_shufflevector(a1, b1, 1, 5);
-                    PX = __builtin_shufflevector(a1, b1, 2, 6), PY = __builtin_shufflevector(a1, b1, 3, 7);
-                    TT = __builtin_shufflevector(a2, b2, 0, 4), RS = __builtin_shufflevector(a2, b2, 1, 5);
-                    SC = __builtin_shufflevector(a2, b2, 2, 6), BM = __builtin_shufflevector(a2, b2, 3, 7);
-                }
+                const f32x2 X = pl2(0, j1, j2), Y = pl2(1, j1, j2), CA = pl2(2, j1, j2), CB = pl2(3, j1, j2);
+                const f32x2 CC = pl2(4, j1, j2), OP = pl2(5, j1, j2), PX = pl2(6, j1, j2), PY = pl2(7, j1, j2);
+                const f32x2 TT = pl2(8, j1, j2), RS = pl2(9, j1, j2), SC = pl2(10, j1, j2), BM = pl2(11, j1, j2);
                 const f32x2 dx = X - f32x2{ppx, ppx}, dy = Y - f32x2{ppy, ppy};
                 const f32x2 q = __builtin_elementwise_fma(CC * dy, dy, (CA * dx) * dx);
                 const f32x2 power = __builtin_elementwise_fma(f32x2{-0.5f, -0.5f}, q, -((CB * dx) * dy));
@@ -901,7 +778,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
         float t_ref = 0.f;
         float ref_t = 0.f, ref_D = 0.f, ref_E = 0.f;  // the last refinement walk's depth, -H', H''
         bool dt_loose = false;  // (SAMPLE) refined, but dT/dt_m continued over too long a step: walked exactly
-        float dT_pre = 0.f;  // (SAMPLE, GSR_SAMPLE_GUESS) a refined root's continued dT/dt_m
+        float dT_pre = 0.f;  // (SAMPLE) a refined root's continued dT/dt_m
         bool passed_grp = false;  // (SAMPLE) left to the passes, which ran in lane groups: median depth in t_ref
         // one pass of the reference's bisection (render_forward.cu:560-645) over
         // the lanes still in range and not refined; FIRST evaluates all 9
@@ -1006,9 +883,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
         // Root refinement for one pixel, shared by the phases below: probe
         // walk + bracketed Halley walks.
         // Up to `walks` Halley walks from t in the bracket [lo, hi] (H(lo) >= 0 >= H(hi)),
-        // tolerances relative to `scale`.  With `ends`, the first walk also evaluates T at the
-        // window ends e0, e8 and sets in_range.  A lane still live on return continues from
-        // (t, lo, hi).
+        // tolerances relative to `scale`.  A lane still live on return continues from (t, lo, hi).
+        // (No walk samples the window ends e0, e8 for in_range: see phase 2 below and DESIGN.md.)
         struct Refine {
             bool refined, ill, in_range, live, newton_done;
             float t_ref, ref_t, ref_D, ref_E;
@@ -1063,8 +939,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 const bool smooth = fabsf(r.t_ref - t) * F <= kCurvTol * D;
                 r.refined = D * tol_cond >= kHNoise && smooth;
                 // (an ill-conditioned root only where T itself is at 1/2: converged by the Newton step)
-                bool ill = GSR_ILL_ACCEPT && !r.refined && newton && D * (kIllTol * scale) >= kHNoise;
-                if (GSR_ILL_NEWTON && ill && !smooth) {
+                bool ill = !r.refined && newton && D * (kIllTol * scale) >= kHNoise;
+                if (ill && !smooth) {
                     // A Halley step long against the curvature length crossed a splat's peak, where H''
                     // flips sign: its iterate is not the root (W16400 case, px (14729, 10): t 5.6e-5
                     // Newton steps before the root next to a peak, H H'' / H'^2 = 0.76, the Halley
@@ -1084,55 +960,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
             }
             t = tn;
         };
-        auto halley = [&](auto&& src, int grouped, bool live, float t, float lo, float hi, bool ends, float e0, float e8, bool in_range0,
-                          int walks, float scale, bool lo_ev, bool hi_ev) {
+        auto halley = [&](auto&& src, int grouped, bool live, float t, float lo, float hi, bool in_range0, int walks,
+                          float scale, bool lo_ev, bool hi_ev) {
             Refine r{false, false, in_range0, false, false, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, lo_ev, hi_ev};
-            const f32x2 TSE[1] = {f32x2{e0, e8}};
             for (int k = 0; k < walks && a.passes > 1; k++) {
                 if (__ballot(live) == 0ull) break;
                 if constexpr (STATS && SAMPLE && !kClock) st_phase = k < 3 ? k : 3;  // (walk stats per walk index)
-                float A = 1.f, B = 1.f, D = 0.f, E = 0.f, F = 0.f;
-                f32x2 AE[1] = {f32x2{1.f, 1.f}}, BE[1] = {f32x2{1.f, 1.f}};
-                float unusedA = 1.f, unusedB = 1.f;
                 const PixSrc ps = src();
 #ifdef GSR_DBG_ROOT
-#ifndef GSR_DBG_ROOT_PX
-#define GSR_DBG_ROOT_PX GSR_DBG_PX
-#define GSR_DBG_ROOT_PY GSR_DBG_PY
-#endif
                 dbg_here = ps.x == (float)GSR_DBG_ROOT_PX && ps.y == (float)GSR_DBG_ROOT_PY;
 #endif
-                if (ends && k == 0) {
-                    walk(ps.mask, ps.plast, ps.x, ps.y, ps.filter, live,
-                         each([&](float alpha, float t_peak, float rs, float sc, float bm) {
-                             refine_step(A, B, D, E, F, t, alpha, t_peak, sc, bm);
-                             bisect_step<1, false>(AE, BE, TSE, unusedA, unusedB, 0.f, alpha, t_peak, rs, sc, bm);
-                         }));
-                } else {
-                    // the two contributor chains of a walk step in packed halves (refine_step2)
-                    f32x2 A2 = {1.f, 1.f}, B2 = {1.f, 1.f}, D2 = {0.f, 0.f}, E2 = {0.f, 0.f}, F2 = {0.f, 0.f};
-                    const f32x2 t2 = {t, t};
-                    walk(ps.mask, ps.plast, ps.x, ps.y, ps.filter, live,
-                         [&](f32x2 alpha, f32x2 t_peak, f32x2 rs, f32x2 sc, f32x2 bm) {
-                             refine_step2(A2, B2, D2, E2, F2, t2, alpha, t_peak, sc, bm);
-                         });
-                    A = A2.x * A2.y;
-                    B = B2.x * B2.y;
-                    D = D2.x + D2.y;
-                    E = E2.x + E2.y;
-                    F = F2.x + F2.y;
-                }
+                // the two contributor chains of a walk step in packed halves (refine_step2)
+                f32x2 A2 = {1.f, 1.f}, B2 = {1.f, 1.f}, D2 = {0.f, 0.f}, E2 = {0.f, 0.f}, F2 = {0.f, 0.f};
+                const f32x2 t2 = {t, t};
+                walk(ps.mask, ps.plast, ps.x, ps.y, ps.filter, live,
+                     [&](f32x2 alpha, f32x2 t_peak, f32x2 rs, f32x2 sc, f32x2 bm) {
+                         refine_step2(A2, B2, D2, E2, F2, t2, alpha, t_peak, sc, bm);
+                     });
+                float A = A2.x * A2.y, B = B2.x * B2.y, D = D2.x + D2.y, E = E2.x + E2.y, F = F2.x + F2.y;
                 A = gprod(A, grouped);
                 B = gprod(B, grouped);
                 D = gsum(D, grouped);
                 E = gsum(E, grouped);
                 F = gsum(F, grouped);
-                if (ends && k == 0) {
-                    const float T0 = gprod(AE[0].x, grouped) * __builtin_amdgcn_rsqf(gprod(BE[0].x, grouped));
-                    const float T8 = gprod(AE[0].y, grouped) * __builtin_amdgcn_rsqf(gprod(BE[0].y, grouped));
-                    r.in_range = r.in_range && T0 >= 0.5f && T8 <= 0.5f;
-                    live = live && r.in_range;
-                }
                 if (live) root_update(r, live, t, lo, hi, A, B, D, E, F, scale);
             }
             if (a.passes == 1 && r.in_range) {  // diagnostic timing of the probe walk alone
@@ -1146,10 +996,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
             r.hi = hi;
             return r;
         };
-        // Probe walk (window ends + m0 + kProbeOffsets * SAMPLE_RANGE), then the
+        // Probe walk (m0 + kProbeOffsets * SAMPLE_RANGE), then the
         // Halley walks from the log-secant root of the bracketing probes.
         auto probe_refine = [&](auto&& src, float pm0, float pT, int grouped, int walks) {
-            bool pin = pT <= kMinTransmittance;
+            const bool pin = pT <= kMinTransmittance;
             const float lo_w = fmaxf(pm0 - a.sample_range, 0.f), hi_w = fmaxf(pm0 + a.sample_range, 0.f);
             const float interval = (hi_w - lo_w) * (1.f / (float)kSplit);
             const float e0 = lo_w, e8 = __builtin_fmaf(interval, (float)kSplit, lo_w);
@@ -1157,7 +1007,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
 #pragma unroll
             for (int s = 0; s < kProbes; s++) {
                 const float off = kProbeOffsets[s] * a.sample_range;
-                tp[s] = kProbeEnds && s == 0 ? e0 : kProbeEnds && s == kProbes - 1 ? e8 : fminf(fmaxf(pm0 + off, e0), e8);
+                tp[s] = fminf(fmaxf(pm0 + off, e0), e8);
             }
             // the m0 probe is the scalar sample, the others go in packed pairs
             constexpr int NP = (kProbes - 1) / 2, MID = (kProbes - 1) / 2;
@@ -1185,7 +1035,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
             }
             Tv[MID] = gprod(A1, grouped) * __builtin_amdgcn_rsqf(gprod(B1, grouped));
             const bool bracketed = (Tv[0] >= 0.5f) && (Tv[kProbes - 1] <= 0.5f);
-            if constexpr (kProbeEnds) pin = bracketed && pin;
             // bracket: the last probe with T >= 1/2 and the next one
             int k1 = 0;
 #pragma unroll
@@ -1204,8 +1053,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
             float wsec = Hlo / (Hlo - Hhi);
             wsec = wsec != wsec ? 0.5f : fminf(fmaxf(wsec, 0.f), 1.f);
             const float t = __builtin_fmaf(wsec, hi - lo, lo);
-            return halley(src, grouped, pin && bracketed, t, lo, hi, false, 0.f, 0.f, pin, walks, fmaxf(t, 1.f), bracketed,
-                          bracketed);
+            return halley(src, grouped, pin && bracketed, t, lo, hi, pin, walks, fmaxf(t, 1.f), bracketed, bracketed);
         };
         bool have_out = false;  // (render path) md_out and dT/dt_m published by the pixel's worker
         if (a.refine && resident && a.passes > 0) {
@@ -1242,7 +1090,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                         if (r.refined && mb != 0.f)
                             dt = (0.5f * 0.69314718055994530942f) * __builtin_fmaf(r.ref_E, mb - r.ref_t, -r.ref_D);
                     }
-                    if (GSR_PASS_SKIP && r.in_range && !r.refined && !r.ill && r.lo_ev && r.hi_ev) {
+                    if (r.in_range && !r.refined && !r.ill && r.lo_ev && r.hi_ev) {
                         flags = kPubBracket;  // (the reference's passes whose cell holds the bracket are skipped)
                         mo = r.lo;
                         s_pub_hi[p] = r.hi;
@@ -1264,13 +1112,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 // that one walk, 99.9% within two; the probe walk (7 samples per contributor) they skip
                 // cost about 1.75 Halley walks.  A pixel with no root among its taps starts from its own
                 // m0.  Those not converged continue in phase 2 on their own lane (as the grid pixels do).
-#ifndef GSR_P1_TWO_LEVEL
-#define GSR_P1_TWO_LEVEL 1
-#endif
-#ifndef GSR_INTERP_SPREAD
-#define GSR_INTERP_SPREAD 0.05f
-#endif
-                constexpr float kInterpSpread = GSR_INTERP_SPREAD;
+                constexpr float kInterpSpread = 0.05f;
                 // (block-uniform) the two-level scheme needs a smooth root field: every 4-grid pixel in range
                 // (T <= MIN_TRANSMITTANCE) and their composite m0 within kInterpSpread of their mean (m0, the
                 // crossing contributor's depth, is known before phase 1; the roots follow it within ~0.05).
@@ -1278,21 +1120,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 // accepted after one walk); the sparse C2 scene's median depth is rough (17% of its tiles, 25%
                 // accepted), and there a tile takes phase 1 as before: its 64 grid pixels probe-walked at once
                 // (a two-level tile that falls back after 1a leaves a wave idle in 1b: C2 0.48 -> 0.505 ms).
-                bool two_level = GSR_P1_TWO_LEVEL;
-                if (two_level) {
-                    float g_min = 3.4e38f, g_max = -3.4e38f, g_sum = 0.f;
-                    bool all_in = true;
+                float g_min = 3.4e38f, g_max = -3.4e38f, g_sum = 0.f;
+                bool all_in = true;
 #pragma unroll
-                    for (int i = 0; i < 16; i++) {
-                        const int q = (i >> 2) * 64 + (i & 3) * 4;
-                        const float gm = s_pub_m0[q];
-                        all_in = all_in && s_pub_T[q] <= kMinTransmittance;
-                        g_min = fminf(g_min, gm);
-                        g_max = fmaxf(g_max, gm);
-                        g_sum += gm;
-                    }
-                    two_level = all_in && g_max - g_min <= kInterpSpread * fmaxf(g_sum * (1.f / 16.f), 1.f);
+                for (int i = 0; i < 16; i++) {
+                    const int q = (i >> 2) * 64 + (i & 3) * 4;
+                    const float gm = s_pub_m0[q];
+                    all_in = all_in && s_pub_T[q] <= kMinTransmittance;
+                    g_min = fminf(g_min, gm);
+                    g_max = fmaxf(g_max, gm);
+                    g_sum += gm;
                 }
+                const bool two_level = all_in && g_max - g_min <= kInterpSpread * fmaxf(g_sum * (1.f / 16.f), 1.f);
                 if (two_level) {
                     {  // phase 1a: (4 (g / 4), 4 (g % 4)), g = lane / 16
                         auto grid4_pixel = [&](int lane) { return ((lane >> 4) >> 2) * 64 + ((lane >> 4) & 3) * 4; };
@@ -1378,10 +1217,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                                 return PixSrc{s_mask + pp, s_pub_last[pp], (float)(x0 + (pp & 15)), (float)(y0 + (pp >> 4)),
                                               0x11111111u << (opaque_int(tid) & 3)};
                             };
-                            const Refine r = interp_tile
-                                                 ? halley(src, 4, qin, t0, e0, e8, false, 0.f, 0.f, qin, 1, fmaxf(t0, 1.f),
-                                                          false, false)
-                                                 : probe_refine(src, qm0, qT, 4, 1);
+                            const Refine r = interp_tile ? halley(src, 4, qin, t0, e0, e8, qin, 1, fmaxf(t0, 1.f), false, false)
+                                                         : probe_refine(src, qm0, qT, 4, 1);
                             if ((tid & 3) == 0) {
                                 const bool cont = r.live;
                                 s_groot[hy * 8 + hx] = (r.in_range && r.refined) ? r.t_ref : cont ? r.t : -1.f;
@@ -1400,14 +1237,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                         return PixSrc{s_mask + gq, s_pub_last[gq], (float)(x0 + (gq & 15)), (float)(y0 + (gq >> 4)),
                                       0x11111111u << (lane & 3)};
                     };
-                    const Refine r = probe_refine(src, gm0, gT, 4, kP1One ? 1 : kRefineWalks);
+                    const Refine r = probe_refine(src, gm0, gT, 4, 1);
                     if (q == 0) {
                         const int lane = opaque_int(tid);
-                        // (kP1One: a grid pixel not converged after its one Halley walk hands its iterate to its
+                        // (a grid pixel not converged after its one Halley walk hands its iterate to its
                         // neighbours as their guess and continues in phase 2 on its own lane)
-                        const bool cont = kP1One && r.live;
+                        const bool cont = r.live;
                         s_groot[lane >> 2] = (r.in_range && r.refined) ? r.t_ref : cont ? r.t : -1.f;
-                        if constexpr (kP1One) s_glive[lane >> 2] = cont ? 1 : 0;
+                        s_glive[lane >> 2] = cont ? 1 : 0;
                         GSR_DBG_NEAR(grid_pixel(lane), "p1 (%d,%d): m0 %.7f -> live %d in %d ref %d ill %d t_ref %.7f D %g\n",
                                      x0 + (grid_pixel(lane) & 15), y0 + (grid_pixel(lane) >> 4), gm0, (int)r.live,
                                      (int)r.in_range, (int)r.refined, (int)r.ill, r.t_ref, r.ref_D);
@@ -1416,7 +1253,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 }
                 __syncthreads();
                 stamp(4);
-                const int skip = (int)(blockIdx.x & 3u);  // the wave left idle (rotated over the SIMDs)
                 if constexpr (STATS) st_phase = 1;
                 bool live2 = false;  // phase-2 pixel not converged after its first walk
                 int p2 = 0;
@@ -1447,9 +1283,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 // grid takes its grid point.  On C3 contributor sets (tools/sim/guess_sim.py) one walk
                 // from it is accepted for 98% of the off-grid pixels, against 90% from the neighbours'
                 // mean.  Any tap without a root (out of range): the mean above.
-#ifndef GSR_P2_INTERP
-#define GSR_P2_INTERP 1
-#endif
                 auto guess_interp = [&](int lx, int ly, float& out) -> bool {
                     int ox[4], oy[4];
                     float wx[4], wy[4];
@@ -1488,14 +1321,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                     out = acc;
                     return ok;
                 };
-                // (kP1One: every lane takes its own pixel — the 192 off-grid ones and the grid pixels phase 1
-                // left live, from their own iterate; otherwise 3 of the 4 waves take the 192 off-grid ones)
-                const int k = kP1One ? tid : (wave < skip ? wave : wave - 1) * 64 + (tid & 63);
-                const int pair = k / 24, r24 = k - pair * 24;
-                const int lx = kP1One ? (tid & 15) : r24 < 8 ? 2 * r24 + 1 : r24 - 8;
-                const int ly = kP1One ? (tid >> 4) : r24 < 8 ? 2 * pair : 2 * pair + 1;
+                // (every lane takes its own pixel: the 192 off-grid ones and the grid pixels phase 1
+                // left live, from their own iterate)
+                const int lx = tid & 15, ly = tid >> 4;
                 const bool on_grid = !(lx & 1) && !(ly & 1);
-                const bool p2_todo = kP1One ? (!on_grid || s_glive[(ly >> 1) * 8 + (lx >> 1)] != 0) : wave != skip;
+                const bool p2_todo = !on_grid || s_glive[(ly >> 1) * 8 + (lx >> 1)] != 0;
                 if (p2_todo) {  // phase 2, first walk
                     const int p = ly * 16 + lx;
                     p2 = p;
@@ -1510,11 +1340,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                     const float interval = (hi_w - lo_w) * (1.f / (float)kSplit);
                     const float e0 = lo_w, e8 = __builtin_fmaf(interval, (float)kSplit, lo_w);
                     float ti = 0.f;
-                    const bool interp = GSR_P2_INTERP && !on_grid && guess_interp(lx, ly, ti);
+                    const bool interp = !on_grid && guess_interp(lx, ly, ti);
                     const float t0 = cnt ? fminf(fmaxf(interp ? ti : sum / (float)cnt, e0), e8) : e0;
                     auto src = [&] { return PixSrc{s_mask + p, ql, qx, qy, ~0u}; };  // (one walk)
-                    const Refine r = halley(src, 1, qin && cnt > 0, t0, e0, e8, !kP2NoEnds, e0, e8, qin, 1, fmaxf(t0, 1.f),
-                                            false, false);
+                    const Refine r = halley(src, 1, qin && cnt > 0, t0, e0, e8, qin, 1, fmaxf(t0, 1.f), false, false);
                     GSR_DBG(p, "p2: m0 %.7f cnt %d t0 %.7f -> live %d in %d ref %d ill %d t_ref %.7f t %.7f [%.7f %.7f] D %g\n",
                             qm0, cnt, t0, (int)r.live, (int)r.in_range, (int)r.refined, (int)r.ill, r.t_ref, r.t, r.lo,
                             r.hi, r.ref_D);
@@ -1548,12 +1377,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 if (live2) s_list[before + __popcll(bl & ((1ull << (tid & 63)) - 1ull))] = (uint8_t)p2;
                 __syncthreads();
                 // group size: as many lanes per pixel as one round of the block allows (4 .. 16)
-#if GSR_P2B_ONE_ROUND
                 int lg2b = 4;
-                while (lg2b > GSR_P2B_ONE_ROUND - 1 && (n_live << lg2b) > (uint32_t)kTilePixels) lg2b--;
-#else
-                const int lg2b = kAdaptGroups ? (n_live <= 16 ? 4 : n_live <= 32 ? 3 : 2) : 2;
-#endif
+                while (lg2b > 0 && (n_live << lg2b) > (uint32_t)kTilePixels) lg2b--;
                 const int G2b = 1 << lg2b;
                 for (uint32_t e = (uint32_t)(tid >> lg2b); e < n_live; e += (uint32_t)(kTilePixels >> lg2b)) {
                     const int p = s_list[e];
@@ -1564,8 +1389,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                         return PixSrc{s_mask + pp, s_pub_last[pp] & kLastMask, (float)(x0 + (pp & 15)), (float)(y0 + (pp >> 4)),
                                       gfilter(G2b, opaque_int(tid) & (G2b - 1))};
                     };
-                    const Refine r = halley(src, G2b, true, t, s_pub_m0[p], s_pub_hi[p], false, 0.f, 0.f, true,
-                                            kP2bWalks, fmaxf(t, 1.f), (sl & kLoEv) != 0u, (sl & kHiEv) != 0u);
+                    const Refine r = halley(src, G2b, true, t, s_pub_m0[p], s_pub_hi[p], true, kP2bWalks, fmaxf(t, 1.f),
+                                            (sl & kLoEv) != 0u, (sl & kHiEv) != 0u);
                     if ((tid & (G2b - 1)) == 0)
                         GSR_DBG(p, "p2b: from %.7f -> live %d in %d ref %d ill %d t_ref %.7f t %.7f [%.7f %.7f] D %g\n", t,
                                 (int)r.live, (int)r.in_range, (int)r.refined, (int)r.ill, r.t_ref, r.t, r.lo, r.hi, r.ref_D);
@@ -1575,18 +1400,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                 stamp(6);
                 const int me = opaque_int(tid);
                 uint32_t flags = s_pub_last[me];
-                if constexpr (kP2NoEnds) {
-                    // phase 2 did not sample the window ends: a root found well inside the reference's
-                    // first window implies its in_range test (T is non-increasing); one near or past an
-                    // end is left to the passes, which decide in_range with their own samples
-                    if (flags & (kPubRefined | kPubIll)) {
-                        const float t_pub = s_pub_T[me] * pixel_ray_norm(lane_fx(), lane_fy(), a.W, a.H, a.focal_x,
-                                                                         a.focal_y);
-                        const float e0 = win_lo(), hi_w = win_hi();
-                        const float e8 = __builtin_fmaf((hi_w - e0) * (1.f / (float)kSplit), (float)kSplit, e0);
-                        const float margin = 1e-4f * fmaxf(t_pub, 1.f);
-                        if (!(t_pub > e0 + margin && t_pub < e8 - margin)) flags = 0u;
-                    }
+                // phase 2 did not sample the window ends: a root found well inside the reference's
+                // first window implies its in_range test (T is non-increasing); one near or past an
+                // end is left to the passes, which decide in_range with their own samples
+                if (flags & (kPubRefined | kPubIll)) {
+                    const float t_pub = s_pub_T[me] * pixel_ray_norm(lane_fx(), lane_fy(), a.W, a.H, a.focal_x, a.focal_y);
+                    const float e0 = win_lo(), hi_w = win_hi();
+                    const float e8 = __builtin_fmaf((hi_w - e0) * (1.f / (float)kSplit), (float)kSplit, e0);
+                    const float margin = 1e-4f * fmaxf(t_pub, 1.f);
+                    if (!(t_pub > e0 + margin && t_pub < e8 - margin)) flags = 0u;
                 }
                 const bool ill = (flags & kPubIll) != 0u;  // root in s_pub_T[me]; dT/dt_m by the walk below
                 if (flags & kPubRefined) {
@@ -1660,8 +1482,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                     // G_p lanes each, the ill-conditioned roots (the dT/dt_m walk only) G_i <= G_p, the
                     // largest powers of two with n_pass G_p + n_ill G_i <= 256 and G_i >= G_p / 8; a
                     // pixel's group is aligned (the pass groups first), so its DPP combine stays inside it
-                    int lgp = kAdaptGroups ? 4 : 0;
-                    while (lgp > 0 && (n_pass << lgp) + n_ill * (uint32_t)max(1, (1 << lgp) >> GSR_P3_ILL_SHIFT) > (uint32_t)kTilePixels)
+                    int lgp = 4;
+                    while (lgp > 0 && (n_pass << lgp) + n_ill * (uint32_t)max(1, (1 << lgp) >> kP3IllShift) > (uint32_t)kTilePixels)
                         lgp--;
                     int lgi = lgp;
                     while (lgi > 0 && (n_pass << lgp) + (n_ill << lgi) > (uint32_t)kTilePixels) lgi--;
@@ -1705,7 +1527,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                             // float64 near-tie either way (tests/flip_audit.py).
                             int skip = 0;
                             const float bhi = work_pass ? s_pub_hi[pw] : -1.f;
-                            if (GSR_PASS_SKIP && bhi >= 0.f) {
+                            if (bhi >= 0.f) {
                                 const float blo = s_pub_T[pw];
                                 const float mg = 1e-6f * fmaxf(bhi, 1.f);
 #pragma unroll 1
@@ -1778,27 +1600,26 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                         in_range = s_pub_last[me] != 0u;
                     }
                 }
-            } else if (GSR_SAMPLE_GUESS) {
+            } else {
                 stamp(2);
                 // SAMPLE (round 5): the query point lies on the other view's median-depth surface, so where
                 // that surface is seen from this view the root is near the point's own distance |p_view|
-                // (pt_t).  The Halley walks start there — the first one also samples the window ends for
-                // the reference's in_range test, as phase 2 of the render path — instead of behind a
-                // 7-probe walk; the bisection fallback of root_update keeps an occluded point's far-off
-                // start inside the window's bracket.
+                // (pt_t).  The Halley walks start there instead of behind a 7-probe walk; the
+                // bisection fallback of root_update keeps an occluded point's far-off start inside the
+                // window's bracket.
                 const bool pin = T <= kMinTransmittance;
                 const float lo_w = win_lo(), hi_w = win_hi();
                 const float e0 = lo_w, e8 = __builtin_fmaf((hi_w - lo_w) * (1.f / (float)kSplit), (float)kSplit, lo_w);
                 const float t0 = fminf(fmaxf(pt_t, e0), e8);
-                // (GSR_SAMPLE_NO_ENDS: every walk the packed two-contributor walk, no window-end samples; a
+                // (every walk the packed two-contributor walk, no window-end samples; a
                 // root found well inside the first window implies the reference's in_range test, T being
                 // non-increasing — the render path's phase-2 argument — and one near or past an end is left
-                // to the passes, which decide in_range with their own samples)
-                const Refine r = halley(own_src, 1, pin, t0, e0, e8, !kSampleNoEnds, e0, e8, pin, kSampleWalks,
-                                        fmaxf(t0, 1.f), false, false);
+                // to the passes, which decide in_range with their own samples; round 5: sample_fwd
+                // 0.839-0.844 -> 0.792-0.812 ms at the sample bench, 2 more of 1.27M points to the passes)
+                const Refine r = halley(own_src, 1, pin, t0, e0, e8, pin, kSampleWalks, fmaxf(t0, 1.f), false, false);
                 in_range = r.in_range;
                 refined = r.refined;
-                if (kSampleNoEnds && refined) {
+                if (refined) {
                     const float margin = 1e-4f * fmaxf(r.t_ref, 1.f);
                     refined = r.t_ref > e0 + margin && r.t_ref < e8 - margin;
                 }
@@ -1819,16 +1640,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                              ? (0.5f * 0.69314718055994530942f) * __builtin_fmaf(ref_E, mb_r - ref_t, -ref_D) : 0.f;
                 if constexpr (STATS && !kClock) st[19] += dt_loose ? 1 : 0;
                 stamp(4);
-            } else {
-                stamp(2);
-                const Refine r = probe_refine(own_src, m_init, T, 1, kRefineWalks);
-                in_range = r.in_range;
-                refined = r.refined;
-                t_ref = r.t_ref;
-                ref_t = r.ref_t;
-                ref_D = r.ref_D;
-                ref_E = r.ref_E;
-                stamp(4);
             }
             // lanes left: the reference's passes from its first window (render path: phase 3 above)
             const bool left = SAMPLE && in_range && !refined;
@@ -1839,7 +1650,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
                     if ((tid & 63) == 0) st[5] += 1;
                 }
                 const int npass = max(a.passes, kSplitIterations);
-                if (GSR_SAMPLE_PASS_GROUP && resident) {
+                if (resident) {
                     // The wave's left points dealt to groups of 16 lanes, 4 points a round: lane q of a group
                     // walks the contributors of index % 16 == q of its point (gfilter) and the group combines
                     // by DPP (gprod) — a fixed group size, so a point's values do not depend on how many
@@ -1951,7 +1762,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
             }
             float dT_dtm = 0.f;
             const bool want_dT = !SAMPLE || a.query == kQuerySample;
-            if (SAMPLE && GSR_SAMPLE_GUESS && refined && !dt_loose) {
+            if (SAMPLE && refined && !dt_loose) {
                 dT_dtm = dT_pre;
             } else if (refined && !dt_loose) {
                 // the reference's dT/dt_m (render_backward.cu:876) is T H' ln2 = H' ln2 / 2 at T = 1/2;
@@ -1966,9 +1777,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
             // blended set, combined by DPP (gsum) and sent back to the owner — instead of every lane of
             // the wave waiting while the few loose ones walk their whole sets (a quarter of the points
             // are loose at the sample bench, in almost every wave)
-            // (GSR_SAMPLE_PASS_GROUP: the points the passes decided, whose dT/dt_m is the exact walk too)
+            // (and the points the passes decided, whose dT/dt_m is the exact walk too)
             float dT_grp = 0.f;
-            const bool grp_dT = SAMPLE && (dt_loose || (GSR_SAMPLE_PASS_GROUP && !refined));
+            const bool grp_dT = SAMPLE && (dt_loose || !refined);
             bool need = false;
             if constexpr (SAMPLE) {
                 need = grp_dT && resident && want_dT && inside && mDepth_b != 0.f && last != 0;

@@ -17,42 +17,22 @@
 // contributor).  No host synchronisation besides the forward's one: the
 // chunk count is derived on the device (sample_setup_kernel) and read
 // together with K.
-// The grouping (round 5, GSR_POINT_SCATTER): the reference sorts the points
+// The grouping (round 5): the reference sorts the points
 // by tile id (SortPairs, stable).  No result depends on the order of a tile's
 // points, so they are scattered instead: the per-tile counts the points
 // kernel already takes are scanned into the tile ranges (sample_setup) and
 // each wave reserves a run of its tile's range with one atomic per distinct
 // tile (sample_scatter_kernel) — one pass over 4 B per point instead of the
 // radix sort's histogram and two onesweep passes (62 + 16 us for 2.07M points
-// at the e2e scene).  Within a wave the points keep their order.
+// at the e2e scene).  Within a wave the points keep their order.  (The sort
+// itself, and a (tile, Morton cell) sort key that makes each wave's points
+// spatially compact — no gain at the benchmark scale, one more sort pass —
+// are recorded in DESIGN.md.)
 #pragma clang fp contract(off)
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #include "gsr_kernels.h"
 
 namespace gsr {
-
-#ifndef GSR_POINT_SCATTER
-#define GSR_POINT_SCATTER 1  // 0: the reference's stable sort by tile id (rocprim radix sort)
-#endif
-using PointSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                   rocprim::default_config, 0>;
-
-// bits to hold 0..tiles (culled points carry key = tiles and sort last).
-// (A (tile, Morton cell) key that makes each wave's points spatially compact
-// was measured: no gain at the benchmark scale, one more sort pass.)
-static unsigned point_key_bits(uint32_t tiles) { return 32u - (unsigned)__builtin_clz(tiles | 1u); }
-
-size_t point_sort_temp_bytes(int PN, uint32_t tiles) {
-    size_t bytes = 0;
-    if (GSR_POINT_SCATTER) return 0;
-    (void)rocprim::radix_sort_pairs<PointSortConfig>(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                     rocprim::counting_iterator<uint32_t>(0), (uint32_t*)nullptr,
-                                                     (size_t)PN, 0u, point_key_bits(tiles));
-    return bytes;
-}
 
 // ndc2Pix in double, as the reference (auxiliary.h:38-40)
 __device__ inline float ndc2pix_d(float v, int S) { return (float)((((double)v + 1.0) * S - 1.0) * 0.5); }
@@ -104,12 +84,7 @@ hipError_t launch_sample_points(const FwdParams& p, int PN, const float* points3
     if (e != hipSuccess || PN == 0) return e;
     hipLaunchKernelGGL(sample_points_kernel, dim3((PN + 255) / 256), dim3(256), 0, stream, PN, points3D, p.view,
                        p.proj, p.W, p.H, p.grid_x, p.grid_y, ps.xy, ps.t, pb.keys_unsorted, st.counts);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (GSR_POINT_SCATTER) return hipSuccess;  // (sample_scatter_kernel, after the setup's scan)
-    size_t bytes = pb.sort_tmp_bytes;
-    return rocprim::radix_sort_pairs<PointSortConfig>(pb.sort_tmp, bytes, pb.keys_unsorted, pb.keys,
-                                                      rocprim::counting_iterator<uint32_t>(0), pb.pt_list,
-                                                      (size_t)PN, 0u, point_key_bits(tiles), stream);
+    return hipGetLastError();  // (the grouping: sample_scatter_kernel, after the setup's scan)
 }
 
 // Block-wide exclusive scan of three counters (1024 lanes = 16 waves).
@@ -179,7 +154,7 @@ __global__ void __launch_bounds__(1024)
     }
 }
 
-// Each point into its tile's range (GSR_POINT_SCATTER): a wave takes one run of
+// Each point into its tile's range: a wave takes one run of
 // slots per distinct tile among its lanes from the end of that tile's range
 // (counts[t] counts down to 0), its lanes in lane order within the run.
 __global__ void __launch_bounds__(256)
@@ -210,16 +185,13 @@ hipError_t launch_sample_setup(int PN, uint32_t tiles, const PointBinState& pb, 
     hipLaunchKernelGGL(sample_setup_kernel, dim3(1), dim3(1024), 0, stream, tiles, st.counts, st.pt_ranges,
                        st.chunk_off, st.totals);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !GSR_POINT_SCATTER || PN == 0) return e;
+    if (e != hipSuccess || PN == 0) return e;
     hipLaunchKernelGGL(sample_scatter_kernel, dim3((PN + 255) / 256), dim3(256), 0, stream, PN, tiles,
                        pb.keys_unsorted, st.counts, st.pt_ranges, pb.pt_list);
     return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ backward
-#ifndef GSR_SAMPLE_BWD_PAIRS
-#define GSR_SAMPLE_BWD_PAIRS 1
-#endif
 struct SampleBwdArgs {
     const uint2* ranges;
     const uint32_t* point_list;
@@ -246,8 +218,8 @@ struct SampleBwdArgs {
     const uint32_t* chunk_order;  // launch order of the chunks (heaviest first) or null
 };
 
-// sampleDepthCUDA backward (sample_backward.cu:77-359), one 256-lane
-// workgroup per chunk, one point per lane.  Per (wave, Gaussian) the 10
+// sampleDepthCUDA backward (sample_backward.cu:77-359), one workgroup per
+// 256-point chunk.  Per (wave, Gaussian) the 10
 // gradient terms are summed by the wave transpose reduction of render_bwd
 // (wave_transpose_reduce16) and added with one atomic instruction into the
 // Gaussian's accumulator record; the point's own gradient (through its
@@ -255,170 +227,7 @@ struct SampleBwdArgs {
 // the point (preprocessPointsCUDA bwd, sample_backward.cu:42-75) is fused at
 // the end.  The grid is an upper bound on the chunk count (read on the
 // device); surplus workgroups exit at once.
-__global__ void __launch_bounds__(256) sample_bwd_kernel(SampleBwdArgs a) {
-    __shared__ float4 s_w0[kTilePixels], s_w1[kTilePixels], s_w2[kTilePixels];
-    __shared__ uint32_t s_id[kTilePixels];
-
-    if (blockIdx.x >= a.totals[2]) return;  // uniform over the block
-    const uint32_t chunk = a.chunk_order ? a.chunk_order[blockIdx.x] : xcd_remap(blockIdx.x, a.totals[2]);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t tile = wave_find_chunk_tile(a.chunk_off, a.num_tiles, chunk);
-    const uint2 range = a.ranges[tile];
-    const int max_contrib = (int)a.chunk_max[chunk];
-    const uint2 pr = a.pt_ranges[tile];
-    const uint32_t slot = pr.x + (chunk - a.chunk_off[tile]) * kTilePixels + tid;
-    const bool in = slot < pr.y;
-    const uint32_t pid = in ? a.pt_list[slot] : 0u;
-
-    // per-point seed (sample_backward.cu:138-158)
-    float pixx = 0.f, pixy = 0.f, mDepth = 0.f, dL_dDepth = 0.f, dpx = 0.f, dpy = 0.f, dT = 0.f;
-    uint32_t last = 0;
-    bool on = false, cached = false;
-    if (in) {
-        const float2 xy = a.pt_xy[pid];
-        pixx = xy.x;
-        pixy = xy.y;
-        last = a.pt_last[pid];
-        mDepth = a.pt_mdepth[pid];
-        const bool in_r = a.inside[pid] != 0;
-        const float g0 = a.dL_doutput[3 * pid], g1 = a.dL_doutput[3 * pid + 1], g2 = a.dL_doutput[3 * pid + 2];
-        const float pnx = (pixx - (float)(a.W - 1) / 2.f) / a.focal_x;
-        const float pny = (pixy - (float)(a.H - 1) / 2.f) / a.focal_y;
-        const float rln = 1.0f / sqrtf(pnx * pnx + pny * pny + 1.f);
-        const float rln2 = 1.f / (pnx * pnx + pny * pny + 1.f);
-        const float depth = mDepth * rln;
-        const float dL_ddepth = g0 * pnx + g1 * pny + g2;
-        dL_dDepth = rln * dL_ddepth;
-        const float aux = dL_ddepth * rln2;
-        dpx = (g0 - aux * pnx) * depth / a.focal_x;
-        dpy = (g1 - aux * pny) * depth / a.focal_y;
-        on = last != 0 && in_r;
-        cached = a.pt_cached[pid] != 0;
-        dT = cached ? a.pt_dT[pid] : 0.f;
-    }
-    const int rounds = (max_contrib + kTilePixels - 1) / kTilePixels;
-    auto stage = [&](int i, bool ids) {
-        const int c = i * kTilePixels + tid;
-        if (c < max_contrib) {
-            const uint32_t g = a.point_list[range.x + c];
-            const Splat* sp = a.splats + g;
-            s_w0[tid] = sp->w0;
-            s_w1[tid] = sp->w1;
-            s_w2[tid] = sp->w2;
-            if (ids) s_id[tid] = g;
-        }
-    };
-
-    // pre-pass dT/dt_m (sample_backward.cu:170-215) unless the forward cached it
-    {
-        const bool need = on && !cached;
-        const uint32_t wave_last = wave_max_u(need ? last : 0u);
-        const bool block_needs = __syncthreads_or(wave_last != 0u);
-        uint32_t c = 0;
-        int toDo = max_contrib;
-        for (int i = 0; block_needs && i < rounds; i++, toDo -= kTilePixels) {
-            __syncthreads();
-            stage(i, false);
-            __syncthreads();
-            const int n = min(kTilePixels, toDo);
-            for (int j = 0; j < n && c < wave_last; j++) {
-                c++;
-                const float4 w0 = s_w0[j], w1 = s_w1[j];
-                const float dx = w0.x - pixx, dy = w0.y - pixy;
-                const float power = splat_power(w0, w1, dx, dy);
-                const float alpha = fminf(0.99f, w1.y * __expf(power));
-                if (!(need && c <= last && !(power > 0.f) && !(alpha < 1.0f / 255.0f))) continue;
-                const float4 w2 = s_w2[j];
-                const float t_peak = splat_tpeak(w1, w2, dx, dy);
-                const float t_delta = (mDepth - t_peak) * w2.y;
-                const float Gt = alpha * __expf(-0.5f * t_delta * t_delta);
-                dT += fast_div(-0.25f * Gt, 1.f - Gt) * fabsf(t_delta) * w2.y;
-            }
-        }
-    }
-    const float kappa = on ? dL_dDepth / fmaxf(-dT, 1e-7f) : 0.f;
-    // contributors past the wave's last are invalid for every lane of it
-    const uint32_t wave_last = wave_max_u(on ? last : 0u);
-
-    // main pass, front to back (sample_backward.cu:228-354)
-    const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;
-    uint32_t contributor = 0;
-    int toDo = max_contrib;
-    for (int i = 0; i < rounds; i++, toDo -= kTilePixels) {
-        __syncthreads();
-        stage(i, true);
-        __syncthreads();
-        const int n = min(kTilePixels, toDo);
-        for (int j = 0; j < n && contributor < wave_last; j++) {
-            contributor++;
-            const float4 w0 = s_w0[j], w1 = s_w1[j];
-            const float dx = w0.x - pixx, dy = w0.y - pixy;
-            const float power = splat_power(w0, w1, dx, dy);
-            const float G = __expf(power);
-            const bool valid = on && contributor <= last && !(power > 0.f) && !(w1.y * G < 1.0f / 255.0f);
-            if (__ballot(valid) == 0ull) continue;  // wave-uniform skip (warp.any)
-            const float4 w2 = s_w2[j];
-            const float alpha = fminf(0.99f, w1.y * G);
-            const float t_peak = splat_tpeak(w1, w2, dx, dy);
-            const float rsig = w2.y;
-            const float t_delta = (mDepth - t_peak) * rsig;
-            const float G_exp = __expf(-0.5f * t_delta * t_delta);
-            const float Gt = alpha * G_exp;
-            float dL_dGt = kappa * 0.25f * fast_rcp(1.f - Gt);
-            dL_dGt = mDepth > t_peak ? dL_dGt : -dL_dGt;
-            dL_dGt = rsig > 0.f ? dL_dGt : 0.f;
-            const float dL_dopa = dL_dGt * G_exp - kappa * (t_delta > 0.f ? 0.5f * fast_rcp(1.f - alpha) : 0.f);
-            const float dL_ddelta = -dL_dGt * Gt * t_delta;
-            const float dL_drsig = dL_ddelta * (mDepth - t_peak);
-            const float dL_dt = -dL_ddelta * rsig;
-            const float dL_dG = w1.y * dL_dopa;
-            const float gdx = G * dx, gdy = G * dy;
-            const float dG_ddelx = -gdx * w0.z - gdy * w0.w;
-            const float dG_ddely = -gdy * w1.x - gdx * w0.w;
-            float dL_ddelx = dL_dG * dG_ddelx + dL_dt * w1.z;
-            float dL_ddely = dL_dG * dG_ddely + dL_dt * w1.w;
-            float f[16];
-#pragma unroll
-            for (int q = 0; q < 16; q++) f[q] = 0.f;
-            if (valid) {
-                dpx -= dL_ddelx;
-                dpy -= dL_ddely;
-                f[kAccMean2D + 0] = dL_ddelx * ddelx_dx;
-                f[kAccMean2D + 1] = dL_ddely * ddely_dy;
-                f[kAccConic + 0] = -0.5f * gdx * dx * dL_dG;
-                f[kAccConic + 1] = -0.5f * gdx * dy * dL_dG;
-                f[kAccConic + 2] = -0.5f * gdy * dy * dL_dG;
-                f[kAccConic + 3] = G * dL_dopa;
-                f[kAccPlane + 0] = dL_dt * dx;
-                f[kAccPlane + 1] = dL_dt * dy;
-                f[kAccPlane + 2] = dL_dt;
-                f[kAccPlane + 3] = dL_drsig;
-            }
-            const float red = wave_transpose_reduce16(f);
-            // lanes 4k hold field k; colour (0-2) and normal (9-11) are zero here
-            const int field = lane >> 2;
-            const bool field_lane = (lane & 3) == 0 && field >= kAccMean2D &&
-                                    (field < kAccNormal || field >= kAccPlane);
-            if (field_lane) atomicAdd(a.acc + (size_t)s_id[j] * kAccFields + field, red);
-        }
-    }
-    if (in) {
-        // dL/dpoints2D in NDC units, then the projection backward
-        // (preprocessPointsCUDA bwd, sample_backward.cu:42-75)
-        const float gx2 = dpx * ddelx_dx, gy2 = dpy * ddely_dy;
-        const float* Pm = a.proj;
-        const float mx = a.points3D[3 * pid], my = a.points3D[3 * pid + 1], mz = a.points3D[3 * pid + 2];
-        const float hw = Pm[3] * mx + Pm[7] * my + Pm[11] * mz + Pm[15];
-        const float m_w = 1.0f / (hw + 0.0000001f);
-        const float mul1 = (Pm[0] * mx + Pm[4] * my + Pm[8] * mz + Pm[12]) * m_w * m_w;
-        const float mul2 = (Pm[1] * mx + Pm[5] * my + Pm[9] * mz + Pm[13]) * m_w * m_w;
-        a.dL_dpoints3D[3 * pid + 0] = (Pm[0] * m_w - Pm[3] * mul1) * gx2 + (Pm[1] * m_w - Pm[3] * mul2) * gy2;
-        a.dL_dpoints3D[3 * pid + 1] = (Pm[4] * m_w - Pm[7] * mul1) * gx2 + (Pm[5] * m_w - Pm[7] * mul2) * gy2;
-        a.dL_dpoints3D[3 * pid + 2] = (Pm[8] * m_w - Pm[11] * mul1) * gx2 + (Pm[9] * m_w - Pm[11] * mul2) * gy2;
-    }
-}
-
-// The same with 2 NPR points per lane (GSR_SAMPLE_BWD_PAIRS): a workgroup of
+// A lane holds 2 NPR points (one point per lane on 256 lanes: rejected): a workgroup of
 // 128 / NPR lanes per 256-point chunk, the lane's points in NPR packed pairs
 // (pair k: points lane + 2k L and lane + (2k + 1) L, L the lane count).  Per
 // (wave, Gaussian) step the record reads, the skip ballot, the transpose
@@ -431,9 +240,7 @@ typedef float sf2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ sf2 ssplat(float v) { return sf2{v, v}; }
 __device__ __forceinline__ sf2 ssel(bool ca, bool cb, sf2 x, sf2 y) { return sf2{ca ? x.x : y.x, cb ? x.y : y.y}; }
 
-#ifndef GSR_SAMPLE_BWD_NPR
-#define GSR_SAMPLE_BWD_NPR 2
-#endif
+constexpr int kSampleBwdNpr = 2;
 
 template <int NPR>
 __global__ void __launch_bounds__(kTilePixels / (2 * NPR)) sample_bwd_pairs_kernel(SampleBwdArgs a) {
@@ -737,11 +544,8 @@ hipError_t launch_sample_bwd(const SampleBwdParams& b, const GeomState& gs, cons
     a.acc = ws.acc;
     a.chunk_order = ws.tile_order;
     const uint32_t bound = sample_chunk_bound(b.PN, tiles);
-    constexpr int kNpr = GSR_SAMPLE_BWD_NPR;
-    if (GSR_SAMPLE_BWD_PAIRS)
-        hipLaunchKernelGGL(sample_bwd_pairs_kernel<kNpr>, dim3(bound), dim3(kTilePixels / (2 * kNpr)), 0, stream, a);
-    else
-        hipLaunchKernelGGL(sample_bwd_kernel, dim3(bound), dim3(kTilePixels), 0, stream, a);
+    hipLaunchKernelGGL(sample_bwd_pairs_kernel<kSampleBwdNpr>, dim3(bound), dim3(kTilePixels / (2 * kSampleBwdNpr)), 0,
+                       stream, a);
     return hipGetLastError();
 }
 

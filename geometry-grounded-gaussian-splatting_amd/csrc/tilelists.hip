@@ -543,10 +543,6 @@ __global__ void __launch_bounds__(64)
     });
 }
 
-#ifndef GSR_TILES_EMIT_SORTED
-#define GSR_TILES_EMIT_SORTED 3  // 3: tiles_emit_coop_kernel (default, grids <= 256 tiles wide), 2: tiles_emit_wide_kernel
-#endif
-
 // tiles_emit_sorted with chunks of 64 NPL entries (NPL per lane: entries
 // c0 + 64 h + lane, h < NPL, with a mask plane each), so the per-chunk work —
 // the bucket scan of chunk_bases, the mask clearing and the barriers — is
@@ -885,7 +881,8 @@ hipError_t launch_list_binning(const FwdParams& p, const GeomState& gs, const in
     if ((e = launch_scan_excl(bs.tiles_count, bs.tiles_off, (size_t)gx * L.nseg_tiles_max, 0u, bs.segbase + gy, gx,
                               sums, stream)) != hipSuccess)
         return e;
-    if (GSR_TILES_EMIT_SORTED == 3 && gx <= (uint32_t)kCoopMaxGx && coop_lds_bytes(gx, gy) <= 65536) {
+    // tiles_emit_coop_kernel where the grid fits it (<= kCoopMaxGx tiles wide), else tiles_emit_wide_kernel
+    if (gx <= (uint32_t)kCoopMaxGx && coop_lds_bytes(gx, gy) <= 65536) {
         // (the coop kernel writes the tile ranges too)
         hipLaunchKernelGGL((tiles_emit_coop_kernel<kCoopWaves, kCoopPlanes>), dim3(kCoopBlocks), dim3(64 * kCoopWaves),
                            coop_lds_bytes(gx, gy), stream, gx, gy, L.nseg_rows, bs.rows_off, last, bs.segbase, bs.rows,

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build an A/B variant of libgsr.so from the working tree with extra defines
 # (development): bash tools/build_variant.sh NAME "-DGSR_X=0 ..." ["FLAGS_file=... (make variables)"]  ->  ab_libs/NAME.so
+# The switches a build can set are listed in DESIGN.md §15 (Build switches).
 set -e
 NAME=$1; DEFS=$2; MAKEVARS=$3
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
