@@ -1394,6 +1394,132 @@ int gsr_knn_mean_dist(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int P, cons
     return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "distCUDA2", e);
 }
 
+namespace {
+// optional per-stage GPU times of gsr_marching_tetrahedra (measurement only): a begin and an end
+// event around each stage, read after the call's last kernel
+struct TetStageTimes {
+    static constexpr int kStages = 7;
+    hipEvent_t ev[kStages][2] = {};
+    bool used[kStages] = {};
+    bool on = false;
+    hipStream_t stream = nullptr;
+    hipError_t begin(int k) {
+        if (!on) return hipSuccess;
+        hipError_t e = hipEventCreate(&ev[k][0]);
+        if (e == hipSuccess) e = hipEventCreate(&ev[k][1]);
+        if (e == hipSuccess) e = hipEventRecord(ev[k][0], stream);
+        used[k] = e == hipSuccess;
+        return e;
+    }
+    hipError_t end(int k) { return on ? hipEventRecord(ev[k][1], stream) : hipSuccess; }
+    hipError_t collect(float* ms) {
+        if (!on) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(stream);
+        for (int k = 0; k < kStages + 1; k++) ms[k] = 0.f;
+        for (int k = 0; k < kStages && e == hipSuccess; k++)
+            if (used[k]) e = hipEventElapsedTime(&ms[k], ev[k][0], ev[k][1]);
+        return e;
+    }
+    ~TetStageTimes() {
+        for (auto& p : ev)
+            for (hipEvent_t x : p)
+                if (x) (void)hipEventDestroy(x);
+    }
+};
+}  // namespace
+
+int gsr_marching_tetrahedra(gsr_alloc_fn edge_alloc, void* edge_ctx, gsr_alloc_fn face_alloc, void* face_ctx,
+                            gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long T, long long V,
+                            const void* tets, int tets_int64, const float* sdf, const uint8_t* valid,
+                            long long* num_edges, long long* num_faces, float* stage_ms, void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_edges || !num_faces) return fail(GSR_ERR_ARGS, "marching_tetrahedra: missing count outputs");
+    *num_edges = *num_faces = 0;
+    if (stage_ms)
+        for (int k = 0; k < 8; k++) stage_ms[k] = 0.f;
+    if (T < 0 || V < 0) return fail(GSR_ERR_ARGS, "marching_tetrahedra: negative size");
+    if (T == 0) return GSR_OK;
+    if (V <= 0) return fail(GSR_ERR_ARGS, "marching_tetrahedra: tets without vertices (V <= 0)");
+    if (!tets || !sdf || !valid) return fail(GSR_ERR_ARGS, "marching_tetrahedra: missing input");
+    if (!edge_alloc || !face_alloc || !scratch_alloc) return fail(GSR_ERR_ARGS, "marching_tetrahedra: missing allocator");
+    if (reinterpret_cast<uintptr_t>(tets) % 16) return fail(GSR_ERR_ARGS, "marching_tetrahedra: tets must be 16-byte aligned");
+    if (V > 0x7fffffffll || T > 0xffffffffll)
+        return fail(GSR_ERR_ARGS, "marching_tetrahedra: more than 2^31 - 1 vertices or 2^32 - 1 tets");
+    const bool is64 = tets_int64 != 0;
+    TetStageTimes times;
+    times.on = stage_ms != nullptr;
+    times.stream = stream;
+
+    TetCountState cs;
+    void* buf = scratch_alloc(scratch_ctx, carve_tet_count(nullptr, V, T, cs));
+    if (!buf) return fail(GSR_ERR_ALLOC, "marching_tetrahedra: scratch allocation failed");
+    carve_tet_count(aligned_base(buf), V, T, cs);
+    GSR_TRY(times.begin(0), "event");
+    GSR_TRY(launch_tet_flags(V, sdf, valid, cs, stream), "tet vertex flags");
+    GSR_TRY(times.end(0), "event");
+    GSR_TRY(times.begin(1), "event");
+    GSR_TRY(launch_tet_count(T, V, tets, is64, cs, stream), "tet count");
+    GSR_TRY(times.end(1), "event");
+
+    // first readback: the totals of one- and two-triangle tets and the bad-id flag
+    ReadbackLease lease;
+    GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+    HostReadback* rb = lease.rb;
+    lease.arm(stream);
+    GSR_TRY(hipMemcpyAsync(rb->pinned, cs.partials + cs.nblocks, sizeof(uint64_t), hipMemcpyDeviceToHost, stream),
+            "memcpy tet counts");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 2, cs.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy vertex id flag");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    lease.recorded();
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    if (rb->pinned[2]) return fail(GSR_ERR_ARGS, "marching_tetrahedra: a tet names a vertex outside [0, V)");
+    const uint64_t n1 = rb->pinned[0], n2 = rb->pinned[1];
+    const uint64_t S = 3 * n1 + 4 * n2, F = n1 + 2 * n2;
+    if (S == 0) {
+        GSR_TRY(times.collect(stage_ms), "stage times");
+        return GSR_OK;
+    }
+    if (S > 0xffffffffull) return fail(GSR_ERR_ARGS, "marching_tetrahedra: more than 2^32 - 1 crossing-edge slots");
+
+    TetEdgeState es;
+    const int bits = tet_key_bits(V);
+    buf = scratch_alloc(scratch_ctx, carve_tet_edges(nullptr, (size_t)S, bits, es));
+    if (!buf) return fail(GSR_ERR_ALLOC, "marching_tetrahedra: scratch allocation failed");
+    carve_tet_edges(aligned_base(buf), (size_t)S, bits, es);
+    GSR_TRY(times.begin(2), "event");
+    GSR_TRY(launch_tet_emit(T, V, tets, is64, cs, es, stream), "tet edge keys");
+    GSR_TRY(times.end(2), "event");
+    GSR_TRY(times.begin(3), "event");
+    GSR_TRY(launch_tet_sort(es, stream), "tet edge sort");
+    GSR_TRY(times.end(3), "event");
+    GSR_TRY(times.begin(4), "event");
+    GSR_TRY(launch_tet_ranks(es, stream), "tet edge ranks");
+    GSR_TRY(times.end(4), "event");
+
+    // second readback: E, the number of distinct keys
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 3, es.heads + (S - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy edge count");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    const uint64_t E = rb->pinned[3];
+    void* edge_ids = edge_alloc(edge_ctx, (size_t)E * 2 * sizeof(long long));
+    if (!edge_ids) return fail(GSR_ERR_ALLOC, "marching_tetrahedra: edge_ids allocation failed");
+    void* faces = face_alloc(face_ctx, (size_t)F * 3 * sizeof(long long));
+    if (!faces) return fail(GSR_ERR_ALLOC, "marching_tetrahedra: faces allocation failed");
+    GSR_TRY(times.begin(5), "event");
+    GSR_TRY(launch_tet_edges(es, (long long*)edge_ids, stream), "tet edges");
+    GSR_TRY(times.end(5), "event");
+    GSR_TRY(times.begin(6), "event");
+    GSR_TRY(launch_tet_faces(T, V, tets, is64, cs, es, (long long*)faces, stream), "tet faces");
+    GSR_TRY(times.end(6), "event");
+    GSR_TRY(times.collect(stage_ms), "stage times");
+    *num_edges = (long long)E;
+    *num_faces = (long long)F;
+    return GSR_OK;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, void* stream_ptr) {
     (void)projmatrix;

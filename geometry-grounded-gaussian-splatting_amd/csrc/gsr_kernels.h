@@ -246,6 +246,43 @@ struct KnnState {
 size_t carve_knn(void* base, int P, KnnState& s);
 hipError_t launch_knn(int P, const float* pts, const KnnState& s, float* mean_dists, hipStream_t stream);
 
+// marching tetrahedra (tetmesh.hip).  Two scratch buffers: the first is sized by V and T alone
+// (V / 4 bytes of vertex flags, 8 bytes per 1024 tets), the second by the number S of crossing-edge
+// slots, known after the count (20 bytes per slot plus the sort's temporary).
+struct TetCountState {
+    long long nblocks;   // ceil(T / 1024)
+    uint32_t* flags;     // 2 bits per vertex: sdf > 0, valid
+    uint64_t* partials;  // [nblocks + 1] (one-triangle | two-triangle << 32) tets per block, then their exclusive scan
+    uint32_t* bad;       // set when a tet names a vertex outside [0, V)
+    void* scan_tmp;
+    size_t scan_tmp_bytes;
+};
+struct TetEdgeState {
+    size_t S;
+    int bits;                // key = a << bits | b
+    uint64_t* keys;          // [S] in slot order
+    uint64_t* keys_sorted;   // [S]
+    uint32_t* slots_sorted;  // [S] the slot of each sorted key
+    uint32_t* heads;         // [S] (over keys) head flags, then the 1-based rank of each sorted key
+    uint32_t* rank;          // [S] (over keys) the mesh vertex of each slot
+    void* tmp;
+    size_t tmp_bytes;
+};
+int tet_key_bits(long long V);
+size_t carve_tet_count(void* base, long long V, long long T, TetCountState& s);
+size_t carve_tet_edges(void* base, size_t S, int bits, TetEdgeState& s);
+hipError_t launch_tet_flags(long long V, const float* sdf, const uint8_t* valid, const TetCountState& s,
+                            hipStream_t stream);
+hipError_t launch_tet_count(long long T, long long V, const void* tets, bool is64, const TetCountState& s,
+                            hipStream_t stream);
+hipError_t launch_tet_emit(long long T, long long V, const void* tets, bool is64, const TetCountState& s,
+                           const TetEdgeState& es, hipStream_t stream);
+hipError_t launch_tet_sort(const TetEdgeState& es, hipStream_t stream);
+hipError_t launch_tet_ranks(const TetEdgeState& es, hipStream_t stream);
+hipError_t launch_tet_edges(const TetEdgeState& es, long long* edge_ids, hipStream_t stream);
+hipError_t launch_tet_faces(long long T, long long V, const void* tets, bool is64, const TetCountState& s,
+                            const TetEdgeState& es, long long* faces, hipStream_t stream);
+
 // Launch order of the per-tile raster kernels, heaviest tile first (longest-
 // processing-time-first list scheduling: the tail of a launch is then made
 // of short tiles).  Cost = the tile's list length (ranges, forward) or its

@@ -247,3 +247,13 @@ def tetra_points(inp):
     local = verts[None] * inp["scales"][:, None]
     corners = (local @ Rm.transpose(1, 2) + inp["means3D"][:, None]).reshape(-1, 3)
     return torch.cat([corners, inp["means3D"]], 0).contiguous()
+
+
+def tetra_points_scale(inp):
+    """The second result of GaussianModel.get_tetra_points
+    (scene/gaussian_model.py:516-518): per tetra point 3 x its Gaussian's
+    largest scale, [15 P, 1] in the order of tetra_points (the 14 offsets of
+    every Gaussian, then the centres) — the edge-length bound of the mesh
+    extraction (mesh_extract_tetrahedra.py:147-150, 166)."""
+    scale = inp["scales"].max(dim=-1, keepdim=True)[0] * 3.0
+    return torch.cat([scale.repeat(1, 14).reshape(-1, 1), scale], 0).contiguous()

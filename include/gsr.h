@@ -506,6 +506,37 @@ int gsr_knn_mean_dist(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int P, cons
                       void* stream);
 
 /*
+ * Marching tetrahedra (the mesh of the offline extraction,
+ * mesh_extract_tetrahedra.py:128-132): replaces the torch function
+ * utils/tetmesh.py:51-190 for one sdf.  tets [T,4] are vertex ids, int32
+ * (tets_int64 == 0) or int64, 16-byte aligned; sdf [V] fp32; valid [V] uint8.
+ * A vertex is positive when sdf > 0; a tet takes part when 1-3 of its
+ * vertices are positive and all four are valid.  Outputs, allocated through
+ * the callbacks once their sizes are known (not called for a size of 0):
+ * edge_ids [E,2] int64, the undirected edges (a, b), a < b, with exactly one
+ * positive end that belong to a participating tet, each once, in ascending
+ * (a, b) order — the mesh vertices; faces [F,3] int64 indices into edge_ids,
+ * in tet order (the reference lists one-triangle tets before two-triangle
+ * tets chunk by chunk; winding and diagonals are the reference's).
+ * scratch_alloc is called twice at most: V / 4 + T / 128 bytes before the
+ * count, then 20 bytes per crossing-edge slot (3 or 4 per participating tet)
+ * plus the radix sort's temporary; both blocks must stay valid until the
+ * call returns (stream-ordered, as gsr_rasterize_forward_ex).  Limits:
+ * V <= 2^31 - 1, T < 2^32, fewer than 2^32 slots.  A vertex id outside
+ * [0, V) is found on the device, reads nothing, and fails the call with
+ * GSR_ERR_ARGS; so do V <= 0 with T > 0 and a NULL input with a non-zero
+ * size.  Synchronises `stream` twice (the slot count, then E), through the
+ * forward's pinned readback slots.  stage_ms (host, 8 floats, may be NULL;
+ * measurement only, adds synchronisation): the GPU milliseconds of the vertex
+ * flags, count + scan, key emission, sort, ranks, edge and face stages, and 0.
+ * The result is the same bits on every run.
+ */
+int gsr_marching_tetrahedra(gsr_alloc_fn edge_alloc, void* edge_ctx, gsr_alloc_fn face_alloc, void* face_ctx,
+                            gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long T, long long V,
+                            const void* tets, int tets_int64, const float* sdf, const uint8_t* valid,
+                            long long* num_edges, long long* num_faces, float* stage_ms, void* stream);
+
+/*
  * Per-stage GPU timing (no reference equivalent; SURVEY §5 "tracing").  While
  * enabled, every kernel stage of the calls above is bracketed by two hipEvents
  * on the call's stream.  gsr_timing_collect() waits for the recorded events,
