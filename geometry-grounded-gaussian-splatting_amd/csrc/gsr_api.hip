@@ -1529,4 +1529,86 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
     return GSR_OK;
 }
 
+long long gsr_densify_workspace_bytes(long long P) {
+    if (P < 1 || P > 0x7fffffffll / 5) return -1;
+    return (long long)densify_workspace_bytes(P);
+}
+
+int gsr_densify_plan(long long P, const float* xyz_gradient_accum, const float* xyz_gradient_accum_abs,
+                     const float* denom, const float* scaling, const float* opacity, float max_grad,
+                     float min_opacity, float pd_extent, void* workspace, long long* counts, float* Q,
+                     void* stream_ptr) {
+    if (!counts) return fail(GSR_ERR_ARGS, "densify plan: missing count output");
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (P < 1) return fail(GSR_ERR_ARGS, "densify plan: no points");
+    if (P > 0x7fffffffll / 5) return fail(GSR_ERR_ARGS, "densify plan: more than (2^31 - 1) / 5 points");
+    if (!xyz_gradient_accum || !xyz_gradient_accum_abs || !denom || !scaling || !opacity || !workspace)
+        return fail(GSR_ERR_ARGS, "densify plan: missing buffer");
+    hipError_t e = launch_densify_plan(P, xyz_gradient_accum, xyz_gradient_accum_abs, denom, scaling, opacity, max_grad,
+                                       min_opacity, pd_extent, workspace, counts, Q, (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "densify plan", e);
+}
+
+int gsr_densify_apply(long long P, const long long* counts, void* workspace, int32_t* map, int build_map,
+                      const float* noise, long long noise_rows, const float* rotation, const float* scaling, int n_params,
+                      const gsr_densify_param* params, void* stream_ptr) {
+    if (P < 1 || P > 0x7fffffffll / 5 || !counts || !workspace)
+        return fail(GSR_ERR_ARGS, "densify apply: invalid arguments");
+    const long long C = counts[0], S = counts[1], pruned = counts[2], N = counts[3];
+    if (C < 0 || C > P || S < 0 || S > 2 * P || pruned < 0 || N < 0 || N != P + C + S - pruned)
+        return fail(GSR_ERR_ARGS, "densify apply: counts are not those of a plan over P points");
+    if (noise_rows != C + 2 * S)
+        return fail(GSR_ERR_ARGS, "densify apply: the noise must have C + 2 S rows of 3");
+    if (n_params < 0 || (n_params > 0 && !params)) return fail(GSR_ERR_ARGS, "densify apply: missing descriptors");
+    if (N == 0) return GSR_OK;
+    if (!map) return fail(GSR_ERR_ARGS, "densify apply: missing map buffer");
+    std::vector<DensifyParam> d((size_t)n_params);
+    for (int k = 0; k < n_params; k++) {
+        const gsr_densify_param& s = params[k];
+        if (s.width < 1 || !s.param || !s.param_out) return fail(GSR_ERR_ARGS, "densify apply: empty descriptor");
+        if (s.role < kDensifyCopy || s.role > kDensifyScaling || (s.role != kDensifyCopy && s.width != 3))
+            return fail(GSR_ERR_ARGS, "densify apply: xyz and scaling rows are 3 wide");
+        if ((s.exp_avg != nullptr) != (s.exp_avg_sq != nullptr) ||
+            (s.exp_avg && (!s.exp_avg_out || !s.exp_avg_sq_out)))
+            return fail(GSR_ERR_ARGS, "densify apply: both moments and both outputs, or none");
+        if (s.role == kDensifyXyz && noise_rows > 0 && (!noise || !rotation || !scaling))
+            return fail(GSR_ERR_ARGS, "densify apply: new positions need noise, rotation and scaling");
+        d[k] = DensifyParam{s.param, s.exp_avg, s.exp_avg_sq, s.param_out, s.exp_avg_out, s.exp_avg_sq_out, s.width,
+                            s.role};
+    }
+    hipError_t e = launch_densify_apply(P, N, C, S, workspace, map, build_map != 0, noise, rotation, scaling, n_params, d.data(),
+                                        (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "densify apply", e);
+}
+
+long long gsr_quantile_workspace_bytes(void) { return (long long)select_workspace_bytes(); }
+
+int gsr_quantile(long long n, const float* values, const float* q, float* out, void* workspace, void* stream_ptr) {
+    if (n < 1 || !values || !q || !out || !workspace) return fail(GSR_ERR_ARGS, "quantile: invalid arguments");
+    hipError_t e = launch_radix_quantile(n, values, q, out, workspace, (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "quantile", e);
+}
+
+int gsr_filter_3d(long long P, const float* xyz, int n_cam, const float* cameras, float max_focal, float* filter_3D,
+                  void* scratch4, void* stream_ptr) {
+    if (P < 1 || n_cam < 1 || !xyz || !cameras || !filter_3D || !scratch4 || !(max_focal > 0.f))
+        return fail(GSR_ERR_ARGS, "filter_3d: invalid arguments");
+    bool any = false;
+    hipError_t e = launch_filter3d(P, xyz, n_cam, cameras, max_focal, filter_3D, (uint32_t*)scratch4, &any,
+                                   (hipStream_t)stream_ptr);
+    if (e != hipSuccess) return fail(GSR_ERR_HIP, "filter_3d", e);
+    if (!any) return fail(GSR_ERR_ARGS, "filter_3d: no point is seen by any camera");
+    return GSR_OK;
+}
+
+int gsr_reset_opacity(long long P, const float* scaling, const float* opacity, const float* filter_3D,
+                      float* opacity_out, float* exp_avg_out, float* exp_avg_sq_out, void* stream_ptr) {
+    if (P < 0 || (P > 0 && (!scaling || !opacity || !filter_3D || !opacity_out)) ||
+        (exp_avg_out != nullptr) != (exp_avg_sq_out != nullptr))
+        return fail(GSR_ERR_ARGS, "reset_opacity: invalid arguments");
+    hipError_t e = launch_reset_opacity(P, scaling, opacity, filter_3D, opacity_out, exp_avg_out, exp_avg_sq_out,
+                                        (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "reset_opacity", e);
+}
+
 }  // extern "C"

@@ -283,6 +283,35 @@ hipError_t launch_tet_edges(const TetEdgeState& es, long long* edge_ids, hipStre
 hipError_t launch_tet_faces(long long T, long long V, const void* tets, bool is64, const TetCountState& s,
                             const TetEdgeState& es, long long* faces, hipStream_t stream);
 
+// densify.hip: densify / prune plan and gather, radix-select quantile, 3D filter, opacity reset
+constexpr int kMaxDensifyParams = 16;
+enum : int { kDensifyCopy = 0, kDensifyXyz = 1, kDensifyScaling = 2 };
+struct DensifyParam {
+    const float* param;       // [P, width]
+    const float* exp_avg;     // [P, width] or null (no optimizer state yet)
+    const float* exp_avg_sq;
+    float* param_out;         // [N, width]
+    float* exp_avg_out;
+    float* exp_avg_sq_out;
+    int width;
+    int role;
+};
+size_t select_workspace_bytes();
+hipError_t launch_radix_quantile(long long n, const float* values, const float* q, float* out, void* workspace,
+                                 hipStream_t stream);
+size_t densify_workspace_bytes(long long P);
+hipError_t launch_densify_plan(long long P, const float* accum, const float* accum_abs, const float* denom,
+                               const float* scaling, const float* opacity, float max_grad, float min_opacity,
+                               float pd_extent, void* workspace, long long* counts_host, float* q_host,
+                               hipStream_t stream);
+hipError_t launch_densify_apply(long long P, long long N, long long C, long long S, void* workspace, int32_t* map,
+                                bool build_map, const float* noise, const float* rotation, const float* scaling, int n,
+                                const DensifyParam* params, hipStream_t stream);
+hipError_t launch_filter3d(long long P, const float* xyz, int n_cam, const float* cams, float focal, float* out,
+                           uint32_t* max_bits, bool* any_seen, hipStream_t stream);
+hipError_t launch_reset_opacity(long long P, const float* scaling, const float* opacity, const float* filter3d,
+                                float* out, float* m, float* v, hipStream_t stream);
+
 // Launch order of the per-tile raster kernels, heaviest tile first (longest-
 // processing-time-first list scheduling: the tail of a launch is then made
 // of short tiles).  Cost = the tile's list length (ranges, forward) or its

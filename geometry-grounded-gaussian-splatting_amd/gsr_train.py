@@ -13,8 +13,9 @@ Per iteration, in the reference's order:
   (render_bwd / preprocess_bwd / sample_bwd ...)  -> densification statistics
   (train.py:236-237, optim.hip)  -> Adam step + zero_grad (train.py:262-263,
   FusedAdam, optim.hip).
-Out of the step, as in the reference's steady state: densify/prune (every 100
-iterations until 15000), the 3D filter recomputation and logging.
+Out of the step, as in the reference's steady state: logging, and what runs
+every 100 iterations until 15000 — densify/prune and the 3D filter
+recomputation, which TrainGaussians offers as methods (gsr_densify, densify.hip).
 
 The torch glue between the kernels (loss arithmetic, the PatchMatch
 projections and masks) is the reference's own torch code restated; the hot
@@ -30,6 +31,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import gsr_densify
 import gsr_scene as S
 from fused_ssim import fused_ssim
 from gaussian_renderer import render, sample_depth
@@ -113,6 +115,21 @@ class TrainGaussians(torch.nn.Module):
                        ("sg_color", self._sg_color, 0.00064)]
         self.optimizer = FusedAdam([{"params": [p], "lr": lr, "name": nm} for nm, p, lr in groups], lr=0.0,
                                    eps=1e-15)
+        self.percent_dense = 0.01  # OptimizationParams.percent_dense (arguments/__init__.py)
+
+    # ---- densification (gaussian_model.py:220-262, 521-539, 797-816; gsr_densify, densify.hip) ----
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size=None, *, noise=None, generator=None):
+        return gsr_densify.densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, noise=noise,
+                                             generator=generator)
+
+    def compute_3D_filter(self, cameras):
+        gsr_densify.compute_3D_filter(self, cameras)
+
+    def reset_3D_filter(self):
+        gsr_densify.reset_3D_filter(self)
+
+    def reset_opacity(self):
+        gsr_densify.reset_opacity(self)
 
     # ---- getters (gaussian_model.py:146-212) ----
     def _cached(self, key, fn):

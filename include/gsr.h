@@ -633,6 +633,94 @@ int gsr_debug_sample_points(const void* point_buffer, int PN, float* median_dept
  */
 int gsr_debug_tile_stats(const void* tile_buffer, int width, int height, uint32_t* max_contrib_out, void* stream);
 
+/*
+ * Densification (csrc/densify.hip): GaussianModel.densify_and_prune
+ * (scene/gaussian_model.py:797-816 with its clone / split / prune helpers),
+ * compute_3D_filter (:225-262) and reset_opacity (:521-539).  Additive to
+ * ABI 20.
+ *
+ * gsr_densify_plan takes the statistics ([P] each), `_scaling` [P,3],
+ * `_opacity` [P] and the scalars max_grad, min_opacity and
+ * percent_dense * extent; on the device it forms grads = accum / denom (NaN
+ * -> 0), ratio = mean(grads >= max_grad), Q = quantile(grads_abs, 1 - ratio)
+ * (torch's linear rule in fp32, by radix select), the reference's clone /
+ * split / opacity-prune decisions for every original point and the scans that
+ * place every surviving or new point.  It synchronises `stream` once to read
+ * counts = {C clones, S split selections (clones that are split again
+ * included), points removed by the opacity prune, N final points}; Q (host,
+ * may be NULL) receives the quantile.  `workspace` is device memory of
+ * gsr_densify_workspace_bytes(P) bytes (-1: P out of range; P <= (2^31 - 1) / 5)
+ * that the following gsr_densify_apply reads.
+ *
+ * gsr_densify_apply writes the new tensors: final layout [surviving originals
+ * | surviving clones | surviving split children, copy 0 | copy 1], each in
+ * source order.  `counts` as the plan returned them; `map` is device memory
+ * of 3 N int32, filled when build_map is non-zero and read otherwise (a caller
+ * that gathers one parameter per call, freeing each source as it goes to bound
+ * the peak memory, builds it in the first call); `noise` [noise_rows, 3] standard-normal draws with
+ * noise_rows == C + 2 S (clones take rows [0, C), the children of the k-th
+ * selected point rows C + k and C + S + k); `rotation` [P,4] and `scaling`
+ * [P,3] are the source `_rotation` and `_scaling` (read by GSR_DENSIFY_XYZ
+ * descriptors only).  Each descriptor gathers
+ * one [P, width] parameter (and its Adam moments, or neither) into [N, width]
+ * outputs, every element written once: survivors keep parameter and moments,
+ * new points copy the parameter with zero moments, except GSR_DENSIFY_XYZ
+ * (new position R(q / |q|) (exp(s) * noise) + source position; the source of
+ * a clone's child is the clone's new position) and GSR_DENSIFY_SCALING
+ * (children: log(exp(s) / 1.6)).  Counts that are inconsistent, a noise buffer
+ * of another size or an incomplete descriptor fail the call; counts that are
+ * not those of the plan in `workspace` make the kernels write nothing.
+ * The result is the same bits on every run.
+ */
+enum gsr_densify_role { GSR_DENSIFY_COPY = 0, GSR_DENSIFY_XYZ = 1, GSR_DENSIFY_SCALING = 2 };
+typedef struct gsr_densify_param {
+    const float* param;
+    const float* exp_avg;
+    const float* exp_avg_sq;
+    float* param_out;
+    float* exp_avg_out;
+    float* exp_avg_sq_out;
+    int width; /* floats per row */
+    int role;  /* enum gsr_densify_role */
+} gsr_densify_param;
+long long gsr_densify_workspace_bytes(long long P);
+int gsr_densify_plan(long long P, const float* xyz_gradient_accum, const float* xyz_gradient_accum_abs,
+                     const float* denom, const float* scaling, const float* opacity, float max_grad,
+                     float min_opacity, float pd_extent, void* workspace, long long* counts, float* Q, void* stream);
+int gsr_densify_apply(long long P, const long long* counts, void* workspace, int32_t* map, int build_map,
+                      const float* noise, long long noise_rows, const float* rotation, const float* scaling, int n_params,
+                      const gsr_densify_param* params, void* stream);
+
+/*
+ * torch.quantile(values, q) with linear interpolation for n non-negative,
+ * non-NaN fp32 values and a device scalar q in [0, 1]: rank = q (n - 1) in
+ * fp32, the order statistics at floor and ceil of it by a radix select over
+ * the bit patterns (no sort, no limit on n), then ATen's lerp.  `out` is a
+ * device float; `workspace` device memory of gsr_quantile_workspace_bytes().
+ */
+long long gsr_quantile_workspace_bytes(void);
+int gsr_quantile(long long n, const float* values, const float* q, float* out, void* workspace, void* stream);
+
+/*
+ * compute_3D_filter: `cameras` is device memory of n_cam records of 14
+ * floats: R (3x3 row-major as the reference stores it, p_cam = p R + T), T,
+ * image_width / Fx * 0.575, image_height / Fy * 0.575.  filter_3D [P]
+ * receives (smallest depth over the cameras that see the point; for unseen
+ * points the largest such depth) / max_focal * sqrt(0.2).  Fails with
+ * GSR_ERR_ARGS when no camera sees any point (the reference raises there).
+ * `scratch4`: 4 bytes of device memory.  Synchronises `stream` once.
+ */
+int gsr_filter_3d(long long P, const float* xyz, int n_cam, const float* cameras, float max_focal, float* filter_3D,
+                  void* scratch4, void* stream);
+
+/*
+ * reset_opacity: opacity_out = inverse_sigmoid(min(sigmoid(o) coef, 0.01) / coef),
+ * coef = sqrt(prod exp(s)^2 / prod (exp(s)^2 + filter_3D^2)); the two moment
+ * outputs (both or neither) are zeroed.
+ */
+int gsr_reset_opacity(long long P, const float* scaling, const float* opacity, const float* filter_3D,
+                      float* opacity_out, float* exp_avg_out, float* exp_avg_sq_out, void* stream);
+
 /* Human-readable message for the last non-OK status on this thread. */
 const char* gsr_last_error(void);
 
