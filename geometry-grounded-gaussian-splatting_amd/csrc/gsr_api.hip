@@ -1520,6 +1520,134 @@ int gsr_marching_tetrahedra(gsr_alloc_fn edge_alloc, void* edge_ctx, gsr_alloc_f
     return GSR_OK;
 }
 
+int gsr_mesh_clusters(gsr_alloc_fn count_alloc, void* count_ctx, gsr_alloc_fn area_alloc, void* area_ctx,
+                      gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long F, long long V, const void* faces,
+                      int faces_int64, const float* vertices, long long* triangle_clusters, long long* num_clusters,
+                      float* stage_ms, void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_clusters) return fail(GSR_ERR_ARGS, "mesh_clusters: missing count output");
+    *num_clusters = 0;
+    if (stage_ms)
+        for (int k = 0; k < 8; k++) stage_ms[k] = 0.f;
+    if (F < 0 || V < 0) return fail(GSR_ERR_ARGS, "mesh_clusters: negative size");
+    if (F == 0) return GSR_OK;
+    if (F >= 0x80000000ll || V > 0x80000000ll)
+        return fail(GSR_ERR_ARGS, "mesh_clusters: 2^31 or more triangles, or more than 2^31 vertices");
+    if (V == 0) return fail(GSR_ERR_ARGS, "mesh_clusters: faces without vertices (V <= 0)");
+    if (!faces || !triangle_clusters) return fail(GSR_ERR_ARGS, "mesh_clusters: missing buffer");
+    if (!count_alloc || !scratch_alloc || (vertices && !area_alloc))
+        return fail(GSR_ERR_ARGS, "mesh_clusters: missing allocator");
+    const bool is64 = faces_int64 != 0, area = vertices != nullptr;
+    TetStageTimes times;
+    times.on = stage_ms != nullptr;
+    times.stream = stream;
+
+    MeshClusterState cs;
+    void* buf = scratch_alloc(scratch_ctx, carve_mesh_clusters(nullptr, F, V, area, cs));
+    if (!buf) return fail(GSR_ERR_ALLOC, "mesh_clusters: scratch allocation failed");
+    carve_mesh_clusters(aligned_base(buf), F, V, area, cs);
+    GSR_TRY(times.begin(0), "event");
+    GSR_TRY(launch_clean_keys(V, faces, is64, cs, stream), "mesh edge keys");
+    GSR_TRY(times.end(0), "event");
+    GSR_TRY(times.begin(1), "event");
+    GSR_TRY(launch_clean_sort(cs, stream), "mesh edge sort");
+    GSR_TRY(times.end(1), "event");
+    GSR_TRY(times.begin(2), "event");
+    GSR_TRY(launch_clean_union(cs, stream), "mesh union");
+    GSR_TRY(times.end(2), "event");
+    GSR_TRY(times.begin(3), "event");
+    GSR_TRY(launch_clean_flatten(cs, stream), "mesh flatten");
+    GSR_TRY(times.end(3), "event");
+    GSR_TRY(times.begin(4), "event");
+    GSR_TRY(launch_clean_ids(cs, stream), "mesh cluster ids");
+    GSR_TRY(times.end(4), "event");
+
+    // the one readback: C and the bad-id flag
+    ReadbackLease lease;
+    GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+    HostReadback* rb = lease.rb;
+    lease.arm(stream);
+    GSR_TRY(hipMemcpyAsync(rb->pinned, cs.cid + F, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy cluster count");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 1, cs.flags + cs.rounds + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy vertex id flag");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    lease.recorded();
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    if (rb->pinned[1]) return fail(GSR_ERR_ARGS, "mesh_clusters: a face names a vertex outside [0, V)");
+    const long long C = rb->pinned[0];
+    void* counts = count_alloc(count_ctx, (size_t)C * sizeof(long long));
+    if (!counts) return fail(GSR_ERR_ALLOC, "mesh_clusters: cluster_n_triangles allocation failed");
+    void* areas = area ? area_alloc(area_ctx, (size_t)C * sizeof(double)) : nullptr;
+    if (area && !areas) return fail(GSR_ERR_ALLOC, "mesh_clusters: cluster_area allocation failed");
+    GSR_TRY(times.begin(5), "event");
+    GSR_TRY(launch_clean_counts(cs, triangle_clusters, (long long*)counts, stream), "mesh cluster counts");
+    GSR_TRY(times.end(5), "event");
+    if (area) {
+        GSR_TRY(times.begin(6), "event");
+        GSR_TRY(launch_clean_area(C, faces, is64, vertices, cs, (double*)areas, stream), "mesh cluster areas");
+        GSR_TRY(times.end(6), "event");
+    }
+    GSR_TRY(times.collect(stage_ms), "stage times");
+    *num_clusters = C;
+    return GSR_OK;
+}
+
+int gsr_mesh_filter(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn face_alloc, void* face_ctx,
+                    gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long F, long long V, long long C,
+                    const float* vertices, const void* faces, int faces_int64, const long long* triangle_clusters,
+                    const long long* cluster_n_triangles, const long long* n_min, long long* num_vertices,
+                    long long* num_faces, void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_vertices || !num_faces) return fail(GSR_ERR_ARGS, "mesh_filter: missing count outputs");
+    *num_vertices = *num_faces = 0;
+    if (F < 0 || V < 0 || C < 0) return fail(GSR_ERR_ARGS, "mesh_filter: negative size");
+    if (F == 0) return GSR_OK;  // no triangle references a vertex
+    if (F >= 0x80000000ll || V >= 0x80000000ll)
+        return fail(GSR_ERR_ARGS, "mesh_filter: 2^31 or more triangles or vertices");
+    if (V == 0 || C == 0) return fail(GSR_ERR_ARGS, "mesh_filter: faces without vertices or clusters");
+    if (!vertices || !faces || !triangle_clusters || !cluster_n_triangles || !n_min)
+        return fail(GSR_ERR_ARGS, "mesh_filter: missing buffer");
+    if (!vertex_alloc || !face_alloc || !scratch_alloc) return fail(GSR_ERR_ARGS, "mesh_filter: missing allocator");
+    const bool is64 = faces_int64 != 0;
+
+    MeshFilterState fs;
+    void* buf = scratch_alloc(scratch_ctx, carve_mesh_filter(nullptr, F, V, fs));
+    if (!buf) return fail(GSR_ERR_ALLOC, "mesh_filter: scratch allocation failed");
+    carve_mesh_filter(aligned_base(buf), F, V, fs);
+    GSR_TRY(launch_filter_plan(F, V, C, faces, is64, triangle_clusters, cluster_n_triangles, n_min, fs, stream),
+            "mesh filter plan");
+
+    // the one readback: V', F' and the bad-id flag
+    ReadbackLease lease;
+    GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+    HostReadback* rb = lease.rb;
+    lease.arm(stream);
+    GSR_TRY(hipMemcpyAsync(rb->pinned, fs.vmap + V, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy vertex count");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 1, fs.fmap + F, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy face count");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 2, fs.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy id flag");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    lease.recorded();
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    if (rb->pinned[2])
+        return fail(GSR_ERR_ARGS, "mesh_filter: a face names a vertex outside [0, V) or a cluster outside [0, C)");
+    const long long Vn = rb->pinned[0], Fn = rb->pinned[1];
+    void* vout = Vn ? vertex_alloc(vertex_ctx, (size_t)Vn * 3 * sizeof(float)) : nullptr;
+    if (Vn && !vout) return fail(GSR_ERR_ALLOC, "mesh_filter: vertices allocation failed");
+    void* fout = Fn ? face_alloc(face_ctx, (size_t)Fn * 3 * sizeof(long long)) : nullptr;
+    if (Fn && !fout) return fail(GSR_ERR_ALLOC, "mesh_filter: faces allocation failed");
+    GSR_TRY(launch_filter_gather(F, V, vertices, faces, is64, fs, (float*)vout, (long long*)fout, stream),
+            "mesh filter gather");
+    *num_vertices = Vn;
+    *num_faces = Fn;
+    return GSR_OK;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, void* stream_ptr) {
     (void)projmatrix;

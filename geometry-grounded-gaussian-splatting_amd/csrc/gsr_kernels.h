@@ -283,6 +283,53 @@ hipError_t launch_tet_edges(const TetEdgeState& es, long long* edge_ids, hipStre
 hipError_t launch_tet_faces(long long T, long long V, const void* tets, bool is64, const TetCountState& s,
                             const TetEdgeState& es, long long* faces, hipStream_t stream);
 
+// mesh clean-up (meshclean.hip).  gsr_mesh_clusters: one scratch buffer sized by F alone (64 bytes per
+// triangle, 8 more with areas, plus the sort's temporary); arrays that are dead by then are reused.
+struct MeshClusterState {
+    long long F;
+    int bits;                // key = a << bits | b
+    int rounds;              // ceil(log2 F) pointer-jumping rounds
+    uint64_t* keys;          // [3 F] slot 3 t + e: edge e of triangle t
+    uint64_t* keys_sorted;   // [3 F]
+    uint32_t* slots_sorted;  // [3 F]
+    uint32_t* parent;        // [F] the union-find forest, parent[x] <= x
+    uint32_t* flags;         // [rounds] a round moved a parent, [rounds + 1] a face names a vertex outside [0, V)
+    uint32_t* cid;           // [F + 1] (over keys) root flags, then their exclusive scan: cid[F] = C
+    uint32_t* root_count;    // [F] (over keys) triangles per root
+    uint32_t* label32;       // [F] (over keys_sorted) cluster id per triangle
+    uint32_t* label_sorted;  // [F] (over keys_sorted)
+    uint32_t* seg;           // [C + 1] (over keys_sorted) first sorted position of every cluster
+    double* tri_area;        // [F] (over slots_sorted)
+    double* area_sorted;     // [F] only with areas
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct MeshFilterState {
+    uint32_t* vmap;  // [V + 1] used flags, then their exclusive scan: the new vertex ids, vmap[V] = V'
+    uint32_t* fmap;  // [F + 1] the same for the triangles that stay
+    uint32_t* bad;
+    void* tmp;
+    size_t tmp_bytes;
+};
+size_t carve_mesh_clusters(void* base, long long F, long long V, bool area, MeshClusterState& s);
+size_t carve_mesh_filter(void* base, long long F, long long V, MeshFilterState& s);
+hipError_t launch_clean_keys(long long V, const void* faces, bool is64, const MeshClusterState& s,
+                             hipStream_t stream);
+hipError_t launch_clean_sort(const MeshClusterState& s, hipStream_t stream);
+hipError_t launch_clean_union(const MeshClusterState& s, hipStream_t stream);
+hipError_t launch_clean_flatten(const MeshClusterState& s, hipStream_t stream);
+hipError_t launch_clean_ids(const MeshClusterState& s, hipStream_t stream);
+hipError_t launch_clean_counts(const MeshClusterState& s, long long* triangle_clusters, long long* cluster_n,
+                               hipStream_t stream);
+hipError_t launch_clean_area(long long C, const void* faces, bool is64, const float* vertices,
+                             const MeshClusterState& s, double* cluster_area, hipStream_t stream);
+hipError_t launch_filter_plan(long long F, long long V, long long C, const void* faces, bool is64,
+                              const long long* clusters, const long long* cluster_n, const long long* n_min,
+                              const MeshFilterState& s, hipStream_t stream);
+hipError_t launch_filter_gather(long long F, long long V, const float* vertices, const void* faces, bool is64,
+                                const MeshFilterState& s, float* vertices_out, long long* faces_out,
+                                hipStream_t stream);
+
 // densify.hip: densify / prune plan and gather, radix-select quantile, 3D filter, opacity reset
 constexpr int kMaxDensifyParams = 16;
 enum : int { kDensifyCopy = 0, kDensifyXyz = 1, kDensifyScaling = 2 };

@@ -1,12 +1,14 @@
-"""Tetrahedral mesh extraction (mesh_extract_tetrahedra.py:64-169 and
+"""Tetrahedral mesh extraction (mesh_extract_tetrahedra.py:18-179 and
 utils/tetmesh.py of the reference) over the C ABI: marching tetrahedra in HIP
-(gsr_marching_tetrahedra, csrc/tetmesh.hip) and the driver around
-gaussian_renderer.integrate.
+(gsr_marching_tetrahedra, csrc/tetmesh.hip), the driver around
+gaussian_renderer.integrate, and the mesh clean-up (gsr_mesh_clusters and
+gsr_mesh_filter, csrc/meshclean.hip).
 
     points = gsr_scene.tetra_points(inp); scale = gsr_scene.tetra_points_scale(inp)
     cells = <the caller's Delaunay triangulation of points, [T, 4]>
     vertices, faces = extract_mesh(points, scale, cells, views, pc, pipe, kernel_size)
     write_ply("recon.ply", vertices, faces)
+    write_ply("recon_post.ply", *post_process_mesh(vertices, faces, cluster_to_keep=1))
 
 Face order: a tet's one or two triangles sit next to each other, in tet
 order.  The reference lists, chunk by chunk, the one-triangle tets before the
@@ -55,14 +57,14 @@ class _Int64Out:
         self.cb = _G._ALLOC(_cb)
 
 
-def _require(t, name, dtypes, ndim):
+def _require(t, name, dtypes, ndim, who="marching_tetrahedra"):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"marching_tetrahedra: `{name}` must be a HIP device tensor")
+        raise RuntimeError(f"{who}: `{name}` must be a HIP device tensor")
     if t.dtype not in dtypes:
-        raise RuntimeError(f"marching_tetrahedra: `{name}` must be {' or '.join(str(d) for d in dtypes)} "
+        raise RuntimeError(f"{who}: `{name}` must be {' or '.join(str(d) for d in dtypes)} "
                            f"(got {t.dtype})")
     if t.dim() != ndim:
-        raise RuntimeError(f"marching_tetrahedra: `{name}` must have {ndim} dimensions (got {tuple(t.shape)})")
+        raise RuntimeError(f"{who}: `{name}` must have {ndim} dimensions (got {tuple(t.shape)})")
 
 
 @torch.no_grad()
@@ -101,6 +103,127 @@ def marching_tetrahedra_ids(tets, sdf, valid):
     if E.value == 0:
         return (torch.zeros(0, 2, dtype=torch.int64, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev))
     return edges.tensor[:2 * E.value].view(-1, 2), faces.tensor[:3 * F.value].view(-1, 3)
+
+
+class _Out:
+    """An output of the C ABI of any dtype, allocated by its callback once the size is known."""
+
+    def __init__(self, device, dtype):
+        self.tensor = torch.empty(0, dtype=dtype, device=device)
+        item = self.tensor.element_size()
+
+        def _cb(_ctx, n):
+            try:
+                self.tensor = torch.empty(int(n) // item, dtype=dtype, device=device)
+                return self.tensor.data_ptr() or 1
+            except Exception:  # noqa: BLE001 - allocation failure is reported as NULL
+                return None
+
+        self.cb = _G._ALLOC(_cb)
+
+
+def _clean_lib():
+    L = _lib()
+    if not getattr(L, "_meshclean_bound", False):
+        vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+        L.gsr_mesh_clusters.restype = i
+        L.gsr_mesh_clusters.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, ll, ll, vp, i, vp, vp,
+                                        ctypes.POINTER(ll), ctypes.POINTER(ctypes.c_float), vp]
+        L.gsr_mesh_filter.restype = i
+        L.gsr_mesh_filter.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, ll, ll, ll, vp, vp, i, vp, vp, vp,
+                                      ctypes.POINTER(ll), ctypes.POINTER(ll), vp]
+        L._meshclean_bound = True
+    return L
+
+
+def _require_mesh(vertices, faces, who, vertices_optional=False):
+    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
+    if faces.size(1) != 3:
+        raise RuntimeError(f"{who}: `faces` must have shape (F, 3) (got {tuple(faces.shape)})")
+    if vertices is None and vertices_optional:
+        return
+    _require(vertices, "vertices", (torch.float32,), 2, who)
+    if vertices.size(1) != 3:
+        raise RuntimeError(f"{who}: `vertices` must have shape (V, 3) (got {tuple(vertices.shape)})")
+    if vertices.device != faces.device:
+        raise RuntimeError(f"{who}: `vertices` and `faces` must be on one device")
+
+
+CLEAN_STAGES = ("keys", "sort", "union", "flatten", "ids", "counts", "area")
+
+
+@torch.no_grad()
+def cluster_connected_triangles(vertices, faces, num_vertices=None):
+    """open3d's TriangleMesh.cluster_connected_triangles on the device
+    (gsr_mesh_clusters, csrc/meshclean.hip): vertices [V,3] float32 or None,
+    faces [F,3] int32 / int64 -> (triangle_clusters [F] int64,
+    cluster_n_triangles [C] int64, cluster_area [C] float64, None without
+    vertices).  Triangles are connected through shared undirected edges;
+    clusters are numbered by their lowest triangle index.  Without vertices,
+    `num_vertices` bounds the ids (default: 2^31, which costs the edge sort its
+    widest keys).  One host readback (C).  Runs on the current stream."""
+    global last_call_stats
+    who = "cluster_connected_triangles"
+    _require_mesh(vertices, faces, who, vertices_optional=True)
+    dev = faces.device
+    F = faces.size(0)
+    V = vertices.size(0) if vertices is not None else (1 << 31 if num_vertices is None else int(num_vertices))
+    labels = torch.empty(F, dtype=torch.int64, device=dev)
+    counts, areas, scratch = _Out(dev, torch.int64), _Out(dev, torch.float64), _G._ScratchBlocks(dev)
+    if F == 0:
+        return labels, counts.tensor, (areas.tensor if vertices is not None else None)
+    L = _clean_lib()
+    faces = faces.contiguous()
+    vertices = vertices.contiguous() if vertices is not None else None
+    C = ctypes.c_longlong(0)
+    ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
+    with torch.cuda.device(dev):
+        rc = L.gsr_mesh_clusters(counts.cb, None, areas.cb, None, scratch.cb, None, F, V, _G._ptr(faces),
+                                 int(faces.dtype == torch.int64), _G._ptr(vertices), _G._ptr(labels), ctypes.byref(C),
+                                 ms, _G._stream(dev))
+    if rc != 0:
+        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+    if last_call_stats is not None:
+        last_call_stats.clear()
+        last_call_stats.update({k: float(ms[i]) for i, k in enumerate(CLEAN_STAGES)},
+                               scratch_bytes=[int(b.numel()) for b in scratch.blocks])
+    return labels, counts.tensor[:C.value], (areas.tensor[:C.value] if vertices is not None else None)
+
+
+@torch.no_grad()
+def post_process_mesh(vertices, faces, cluster_to_keep=1, min_triangles=50):
+    """mesh_extract_tetrahedra.py:18-40 post_process_mesh on the device:
+    keeps the clusters of connected triangles with at least
+    max(sorted(cluster_n_triangles)[-cluster_to_keep], min_triangles)
+    triangles (ties at the threshold all stay), then drops the unreferenced
+    vertices, then the triangles with two equal vertex ids.  vertices [V,3]
+    float32, faces [F,3] int32 / int64 -> (vertices [V',3] float32, faces
+    [F',3] int64), order and winding kept.  The threshold never leaves the
+    device; the host reads three sizes (C, then V' and F' together)."""
+    who = "post_process_mesh"
+    _require_mesh(vertices, faces, who)
+    if isinstance(cluster_to_keep, bool) or not isinstance(cluster_to_keep, int) or cluster_to_keep < 1:
+        raise ValueError(f"{who}: `cluster_to_keep` must be an integer >= 1 (got {cluster_to_keep!r})")
+    dev = faces.device
+    F, V = faces.size(0), vertices.size(0)
+    if F == 0:
+        return (torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev))
+    faces, vertices = faces.contiguous(), vertices.contiguous()
+    labels, counts, _ = cluster_connected_triangles(None, faces, num_vertices=V)
+    C = counts.size(0)
+    if cluster_to_keep > C:
+        raise ValueError(f"{who}: `cluster_to_keep` = {cluster_to_keep} but the mesh has {C} clusters")
+    n_min = torch.sort(counts).values[C - cluster_to_keep].clamp(min=int(min_triangles)).reshape(1).contiguous()
+    L = _clean_lib()
+    vout, fout, scratch = _Out(dev, torch.float32), _Out(dev, torch.int64), _G._ScratchBlocks(dev)
+    Vn, Fn = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    with torch.cuda.device(dev):
+        rc = L.gsr_mesh_filter(vout.cb, None, fout.cb, None, scratch.cb, None, F, V, C, _G._ptr(vertices),
+                               _G._ptr(faces), int(faces.dtype == torch.int64), _G._ptr(labels), _G._ptr(counts),
+                               _G._ptr(n_min), ctypes.byref(Vn), ctypes.byref(Fn), _G._stream(dev))
+    if rc != 0:
+        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+    return vout.tensor[:3 * Vn.value].view(-1, 3), fout.tensor[:3 * Fn.value].view(-1, 3)
 
 
 def _unbatched(vertices, tets, sdf, scales, valids):
@@ -169,13 +292,15 @@ def alpha_cull_sdf(points, views, pc, pipe, kernel_size, chunk=10_000_000):
 
 
 @torch.no_grad()
-def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_binary_steps=10):
+def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_binary_steps=10, cluster_to_keep=None):
     """mesh_extract_tetrahedra.py:123-169: the level set sdf = 0 of
     alpha_cull_sdf over the tets `cells` [T,4] of `points` [V,3]
     (`points_scale` [V,1]: gsr_scene.tetra_points_scale), every vertex bisected
     n_binary_steps times along its edge; vertices whose edge is longer than
     the two ends' scales and the faces that use them are dropped.
-    -> vertices [N,3] float32, faces [M,3] int64."""
+    -> vertices [N,3] float32, faces [M,3] int64 (the geometry of recon.ply).
+    With an integer `cluster_to_keep` the result goes through
+    post_process_mesh (the geometry of recon_post.ply)."""
     sdf, valid = alpha_cull_sdf(points, views, pc, pipe, kernel_size)
     verts_list, scale_list, faces_list, _ = marching_tetrahedra(points[None], cells, sdf[None], points_scale[None], valid[None])
     end_points, end_sdf = verts_list[0]
@@ -200,7 +325,10 @@ def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_bi
     used = torch.zeros(vertices.shape[0], dtype=torch.bool, device=vertices.device)
     used[faces.reshape(-1)] = True
     remap = torch.cumsum(used, 0) - 1
-    return vertices[used].float().contiguous(), remap[faces].contiguous()
+    vertices, faces = vertices[used].float().contiguous(), remap[faces].contiguous()
+    if cluster_to_keep is not None:
+        return post_process_mesh(vertices, faces, cluster_to_keep)
+    return vertices, faces
 
 
 def write_ply(path, vertices, faces):

@@ -537,6 +537,55 @@ int gsr_marching_tetrahedra(gsr_alloc_fn edge_alloc, void* edge_ctx, gsr_alloc_f
                             long long* num_edges, long long* num_faces, float* stage_ms, void* stream);
 
 /*
+ * Mesh clean-up (the reference's post_process_mesh,
+ * mesh_extract_tetrahedra.py:18-40, which runs open3d on the CPU), in two
+ * calls.
+ *
+ * gsr_mesh_clusters is open3d's cluster_connected_triangles: faces [F,3] are
+ * vertex ids, int32 (faces_int64 == 0) or int64; vertices [V,3] fp32 may be
+ * NULL (no areas; V is then only the bound of the ids, at most 2^31).  Two
+ * triangles are adjacent when they share an undirected edge (min, max) of
+ * vertex ids: a shared vertex alone does not connect, an edge of three or
+ * more triangles connects them all, and the edges of index-degenerate
+ * triangles count like any other.  Outputs: triangle_clusters [F] int64 (the
+ * caller's buffer), the cluster of every triangle, clusters numbered in
+ * ascending order of their lowest triangle index; *num_clusters = C; through
+ * the callbacks once C is known (not called when F == 0):
+ * cluster_n_triangles [C] int64 and, with vertices, cluster_area [C] float64
+ * (0.5 |cross| per triangle, computed and summed in float64 in a fixed order).
+ * scratch_alloc is called once: 64 bytes per triangle (72 with areas) plus
+ * the radix sort's temporary; the block must stay valid until the call
+ * returns (stream-ordered).  Limits: F < 2^31, V <= 2^31.  A vertex id
+ * outside [0, V) is found on the device, reads nothing, and fails the call
+ * with GSR_ERR_ARGS.  Synchronises `stream` once (C).  stage_ms (host, 8
+ * floats, may be NULL; measurement only, adds synchronisation): the GPU
+ * milliseconds of the key, sort, union, flatten, cluster-id, count and area
+ * stages, and 0.  The result is the same bits on every run.
+ *
+ * gsr_mesh_filter removes, in this order, the triangles whose cluster has
+ * fewer than *n_min triangles (n_min: one int64 in device memory, so a
+ * threshold computed on the device needs no readback), the vertices no
+ * remaining triangle references, and the remaining triangles with two equal
+ * vertex ids (vertices orphaned only by this last step stay, as in open3d's
+ * call order).  triangle_clusters [F] and cluster_n_triangles [C] are
+ * gsr_mesh_clusters' outputs.  Outputs through the callbacks (not called for
+ * a size of 0): vertices [V',3] fp32 and faces [F',3] int64, both in their
+ * input order, winding kept.  scratch_alloc is called once (4 bytes per
+ * vertex and per triangle plus a scan's temporary).  Limits: F, V < 2^31.
+ * An id outside its range fails the call with GSR_ERR_ARGS.  Synchronises
+ * `stream` once (V' and F').  The result is the same bits on every run.
+ */
+int gsr_mesh_clusters(gsr_alloc_fn count_alloc, void* count_ctx, gsr_alloc_fn area_alloc, void* area_ctx,
+                      gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long F, long long V, const void* faces,
+                      int faces_int64, const float* vertices, long long* triangle_clusters, long long* num_clusters,
+                      float* stage_ms, void* stream);
+int gsr_mesh_filter(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn face_alloc, void* face_ctx,
+                    gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long F, long long V, long long C,
+                    const float* vertices, const void* faces, int faces_int64, const long long* triangle_clusters,
+                    const long long* cluster_n_triangles, const long long* n_min, long long* num_vertices,
+                    long long* num_faces, void* stream);
+
+/*
  * Per-stage GPU timing (no reference equivalent; SURVEY §5 "tracing").  While
  * enabled, every kernel stage of the calls above is bracketed by two hipEvents
  * on the call's stream.  gsr_timing_collect() waits for the recorded events,
