@@ -64,6 +64,9 @@ struct DsortState {
     int tiles;
 };
 
+// keys per workgroup tile for P keys (gsr_debug_depth_sort_tile_keys)
+int dsort_tile_keys(int P) { return kDsThreads * dsort_items(P); }
+
 static int dsort_tiles(int P) {
     const int tile = kDsThreads * dsort_items(P);
     return (P + tile - 1) / tile;

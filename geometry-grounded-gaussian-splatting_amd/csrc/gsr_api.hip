@@ -462,6 +462,56 @@ int gsr_debug_tile_stats(const void* tile_buffer, int width, int height, uint32_
     return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug tile stats", e);
 }
 
+int gsr_debug_depth_sort_tile_keys(int P) { return P < 0 ? -1 : gsr::dsort_tile_keys(P); }
+
+// the GeomState fields the depth sort touches that the caller does not pass, carved out of `scratch`
+static size_t carve_depth_sort(void* base, int P, GeomState& g) {
+    Carver c(base);
+    g.tiles_touched = c.take<uint32_t>(P);
+    g.offsets_K = c.take<uint32_t>(1);
+    g.dsort_tmp_bytes = depth_sort_temp_bytes(P);
+    g.dsort_tmp = c.take<char>(g.dsort_tmp_bytes);
+    // never fewer bytes for more keys: where the sort switches to its larger tile its look-back state
+    // halves (dsort_temp_bytes drops by ~0.7 MB from 2,000,000 to 2,000,001 keys), so the small tile's
+    // state (4 passes x 256 words per tile) is reserved on top there
+    const int t0 = dsort_tile_keys(0);
+    const size_t slack = dsort_tile_keys(P) > t0 ? (size_t)4 * 256 * sizeof(uint32_t) * ((P + t0 - 1) / t0) : 0;
+    return c.off + slack + 256;
+}
+
+long long gsr_debug_depth_sort_bytes(int P) {
+    if (P < 0) return -1;
+    GeomState g{};
+    return (long long)carve_depth_sort(nullptr, P, g);
+}
+
+int gsr_debug_depth_sort(int P, const uint32_t* keys, uint32_t* keys_sorted, uint32_t* order, void* scratch,
+                         int prepared, void* stream_ptr) {
+    if (P < 0) return fail(GSR_ERR_ARGS, "invalid arguments");
+    if (P == 0) return GSR_OK;
+    if (!keys || !keys_sorted || !order || !scratch) return fail(GSR_ERR_ARGS, "invalid arguments");
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    GeomState gs{};
+    carve_depth_sort(aligned_base(scratch), P, gs);
+    gs.depths = reinterpret_cast<float*>(const_cast<uint32_t*>(keys));  // (read only)
+    gs.depth_keys_sorted = keys_sorted;
+    gs.order = order;
+    hipError_t e = hipSuccess;
+    if (prepared) {
+        // what the preprocess leaves behind on the render path: the sort's state and K zeroed; then
+        // the fused count + histogram kernel
+        uint32_t* first = nullptr;
+        size_t words = 0;
+        dsort_zero_region(gs.dsort_tmp, P, &first, &words);
+        e = hipMemsetAsync(first, 0, words * sizeof(uint32_t), stream);
+        if (e == hipSuccess) e = hipMemsetAsync(gs.tiles_touched, 0, sizeof(uint32_t) * (size_t)P, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(gs.offsets_K, 0, sizeof(uint32_t), stream);
+        if (e == hipSuccess) e = launch_count_k_hist(gs, P, true, stream);
+    }
+    if (e == hipSuccess) e = launch_depth_sort(gs, P, prepared != 0, stream);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug depth sort", e);
+}
+
 int gsr_set_option(int opt, int value) {
     if (opt < 0 || opt >= gsr::kNumOptions || gsr::option_retired(opt)) return fail(GSR_ERR_ARGS, "unknown option");
     gsr::g_options[opt] = value;

@@ -75,6 +75,7 @@ size_t sort_temp_bytes(int K, int tile_bits);
 hipError_t launch_depth_sort(const GeomState& gs, int P, bool prepared, hipStream_t stream);
 // dsort.hip
 size_t dsort_temp_bytes(int P);
+int dsort_tile_keys(int P);
 void dsort_zero_region(void* base, int P, uint32_t** first, size_t* words);
 // K into gs.offsets_K and, with `hist`, the depth-key digit histograms (both zeroed by the preprocess)
 hipError_t launch_count_k_hist(const GeomState& gs, int P, bool hist, hipStream_t stream);

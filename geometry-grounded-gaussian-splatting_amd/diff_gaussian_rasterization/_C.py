@@ -107,6 +107,12 @@ def _load():
     L.gsr_debug_tile_stats.argtypes = [vp, i, i, vp, vp]
     L.gsr_debug_sample_points.argtypes = [vp, i, vp, vp, vp]
     L.gsr_debug_render_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i]
+    L.gsr_debug_depth_sort_tile_keys.restype = i
+    L.gsr_debug_depth_sort_tile_keys.argtypes = [i]
+    L.gsr_debug_depth_sort_bytes.restype = ctypes.c_longlong
+    L.gsr_debug_depth_sort_bytes.argtypes = [i]
+    L.gsr_debug_depth_sort.restype = i
+    L.gsr_debug_depth_sort.argtypes = [i, vp, vp, vp, vp, i, vp]
     L.gsr_timing_enable.argtypes = [i]
     L.gsr_timing_stage_mask.argtypes = [ctypes.c_uint]
     L.gsr_timing_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i)]
@@ -208,6 +214,52 @@ def debug_sample_points(pointBuffer, PN: int):
                                            md.ctypes.data_as(ctypes.c_void_p), last.ctypes.data_as(ctypes.c_void_p),
                                            ctypes.c_void_p(stream)))
     return md, last
+
+
+def debug_depth_sort_tile_keys(P: int) -> int:
+    """Keys per workgroup tile of dsort.hip for P keys (gsr_debug_depth_sort_tile_keys;
+    host only, no GPU needed)."""
+    n = _load().gsr_debug_depth_sort_tile_keys(int(P))
+    if n < 0:
+        raise RuntimeError(f"gsr: debug_depth_sort_tile_keys({P}): P must be >= 0")
+    return n
+
+
+def debug_depth_sort_bytes(P: int) -> int:
+    """Scratch bytes of debug_depth_sort for P keys (gsr_debug_depth_sort_bytes; host only)."""
+    n = _load().gsr_debug_depth_sort_bytes(int(P))
+    if n < 0:
+        raise RuntimeError(f"gsr: debug_depth_sort_bytes({P}): P must be >= 0")
+    return n
+
+
+def debug_depth_sort(keys, prepared: bool = True):
+    """(order [P] int32, keys_sorted [P]) = the depth sort of the render path
+    (gsr_debug_depth_sort) on the caller's 32-bit keys, taken as unsigned bit
+    patterns: the stable ascending order, values = index.  `prepared`: the
+    state cleared and the histograms counted as the render path does, else by
+    the sort's own kernels.  No host synchronisation."""
+    bits32 = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda:
+        raise RuntimeError("gsr debug_depth_sort: `keys` must be a HIP device tensor")
+    if keys.dtype not in bits32 or keys.dim() != 1:
+        raise RuntimeError(f"gsr debug_depth_sort: `keys` must be a 1-D int32 / uint32 tensor (got {keys.dtype}, "
+                           f"{keys.dim()}-D)")
+    if not keys.is_contiguous():
+        raise RuntimeError("gsr debug_depth_sort: `keys` must be contiguous")
+    L = _load()
+    P = keys.numel()
+    if P >= 2 ** 31:
+        raise RuntimeError("gsr debug_depth_sort: at most 2^31 - 1 keys")
+    order = torch.empty(P, dtype=torch.int32, device=keys.device)
+    keys_sorted = torch.empty_like(keys)
+    if P == 0:
+        return order, keys_sorted
+    scratch = torch.empty(L.gsr_debug_depth_sort_bytes(P), dtype=torch.uint8, device=keys.device)
+    with torch.cuda.device(keys.device):
+        _check(L.gsr_debug_depth_sort(P, _ptr(keys), _ptr(keys_sorted), _ptr(order), _ptr(scratch),
+                                      int(bool(prepared)), _stream(keys.device)))
+    return order, keys_sorted
 
 
 def set_option(opt: int, value: int) -> None:

@@ -683,6 +683,23 @@ int gsr_debug_sample_points(const void* point_buffer, int PN, float* median_dept
 int gsr_debug_tile_stats(const void* tile_buffer, int width, int height, uint32_t* max_contrib_out, void* stream);
 
 /*
+ * The depth sort on the caller's keys (test hook, no reference equivalent;
+ * additive to ABI 20).  All pointers but `stream` are device memory.
+ */
+/* host only: keys per dsort.hip workgroup tile for P keys (6144, or 12288 above 2,000,000); -1 for P < 0 */
+int gsr_debug_depth_sort_tile_keys(int P);
+/* bytes of `scratch` for P keys; -1 for P < 0 */
+long long gsr_debug_depth_sort_bytes(int P);
+/* order[P], keys_sorted[P] = the stable sort of keys[P] (values = index), by launch_depth_sort:
+ * dsort.hip, or rocPRIM under GSR_OPT_ROCPRIM_DSORT.
+ * prepared != 0: as the render path, with the state cleared up front (dsort_zero_region) and the
+ * histograms from count_k_hist_kernel over a zeroed tiles_touched, then launch_depth_sort(..., true).
+ * prepared == 0: the sort's own zero and histogram kernels.
+ * P == 0 succeeds and writes nothing.  Stream-ordered, no host synchronisation. */
+int gsr_debug_depth_sort(int P, const uint32_t* keys, uint32_t* keys_sorted, uint32_t* order,
+                         void* scratch, int prepared, void* stream);
+
+/*
  * Densification (csrc/densify.hip): GaussianModel.densify_and_prune
  * (scene/gaussian_model.py:797-816 with its clone / split / prune helpers),
  * compute_3D_filter (:225-262) and reset_opacity (:521-539).  Additive to

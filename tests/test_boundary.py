@@ -274,3 +274,55 @@ def test_empty_scene_matches_reference_semantics():
     assert out[0] == 0
     assert out[1].shape == (3, 6, 10) and float(out[1].abs().sum()) == 0.0
     assert out[5].shape == (0,)
+
+
+def test_debug_depth_sort_refuses_cpu_and_bad_dtypes():
+    """debug_depth_sort takes 32-bit integer HIP tensors only: no CPU
+    fall-back, no silent conversion of other dtypes or shapes."""
+    from diff_gaussian_rasterization import _C
+
+    with pytest.raises(RuntimeError, match="HIP device tensor"):
+        _C.debug_depth_sort(torch.zeros(8, dtype=torch.int32), True)
+    with pytest.raises(RuntimeError, match="HIP device tensor"):
+        _C.debug_depth_sort(torch.zeros(16, dtype=torch.int32)[::2], False)
+    with pytest.raises(RuntimeError, match="HIP device tensor"):
+        _C.debug_depth_sort([3, 1, 2], True)
+    # the dtype / shape check needs no device: a meta tensor reports is_cuda False, so drive the check
+    # through a stand-in that claims to live on the device
+    class _Dev(torch.Tensor):
+        is_cuda = True
+
+    for bad in (torch.zeros(8), torch.zeros(8, dtype=torch.int64), torch.zeros(8, dtype=torch.int16),
+                torch.zeros(8, dtype=torch.float64), torch.zeros(4, 2, dtype=torch.int32)):
+        with pytest.raises(RuntimeError, match="1-D int32 / uint32"):
+            _C.debug_depth_sort(bad.as_subclass(_Dev), True)
+    with pytest.raises(RuntimeError, match="must be contiguous"):
+        _C.debug_depth_sort(torch.zeros(16, dtype=torch.int32)[::2].as_subclass(_Dev), True)
+
+
+def test_debug_depth_sort_sizes_host_only():
+    """The tile size and scratch size of the depth-sort hook are host-only
+    calls: -1 (an error in the binding) for P < 0, two tile sizes with the
+    switch after 2,000,000 keys, and scratch bytes that never shrink as P
+    grows over the sizes tests/test_gpu_dsort.py sorts."""
+    from diff_gaussian_rasterization import _C
+
+    lib = ctypes.CDLL(_C.loaded_library_path())
+    lib.gsr_debug_depth_sort_bytes.restype = ctypes.c_longlong
+    for P in (-1, -6144, -2 ** 31):
+        assert lib.gsr_debug_depth_sort_tile_keys(ctypes.c_int(P)) == -1
+        assert lib.gsr_debug_depth_sort_bytes(ctypes.c_int(P)) == -1
+        with pytest.raises(RuntimeError, match="P must be >= 0"):
+            _C.debug_depth_sort_tile_keys(P)
+        with pytest.raises(RuntimeError, match="P must be >= 0"):
+            _C.debug_depth_sort_bytes(P)
+    t, tb = _C.debug_depth_sort_tile_keys(1), _C.debug_depth_sort_tile_keys(2_000_001)
+    assert t > 0 and tb > 0 and t != tb
+    assert _C.debug_depth_sort_tile_keys(0) == _C.debug_depth_sort_tile_keys(2_000_000) == t
+    sizes = sorted({0, 1, 63, 64, 65, t - 1, t, t + 1, 32 * t, 32 * t + 1, 33 * t + 1, 64 * t + 1, 96 * t + 1,
+                    128 * t, 128 * t + 1, 129 * t + 1, 2_000_000, 2_000_001, 163 * tb, 163 * tb + 1})
+    nbytes = [_C.debug_depth_sort_bytes(P) for P in sizes]
+    assert all(b > 0 for b in nbytes)
+    assert all(a <= b for a, b in zip(nbytes, nbytes[1:])), list(zip(sizes, nbytes))
+    # room for what the hook carves: tiles_touched [P], the sort's alternate keys and values [P] each
+    assert all(b >= 12 * P for P, b in zip(sizes, nbytes))

@@ -118,7 +118,7 @@ def _run(c, colors_precomp=None, cov3D=None, scale_modifier=1.0, check_bwd=True,
         assert float(normal.abs().max()) == 0.0 and float(mdepth.abs().max()) == 0.0
     _audit_full_images(c, out, o)
     if not check_bwd:
-        return
+        return out, o, None, None
     g = S.upstream_grads(c["H"], c["W"])
     g["alpha"] = torch.randn(1, c["H"], c["W"], generator=torch.Generator().manual_seed(5)) * 1e-3
     b = _oracle_backward_on_gpu_state(c, a, out, o, g)
@@ -414,11 +414,14 @@ def test_parity_depth_ties():
     _run(_with_depth_ties(Hh.small_case(P=600, W=64, H=48, seed=21), 250))
 
 
-@pytest.mark.parametrize("P", [1, 7, 4095, 4097, 9000])
+@pytest.mark.parametrize("P", [1, 7, 4095, 4097, 9000, 6143, 6144, 6145, 12289])
 def test_parity_depth_sort_tiles(P):
-    """dsort.hip's 4096-key tiles: sizes below, at and across tile
+    """dsort.hip's 6144-key tiles under real preprocess output (the fused
+    count + histogram kernel): sizes below, at and across one and two tile
     boundaries (the last tile's padding keys), with depth ties, against the
-    oracle's stable order."""
+    oracle's stable order.  (4095, 4097 and 9000 date from 4096-key tiles and
+    stay as ordinary sizes; tests/test_gpu_dsort.py runs the sort alone at
+    every structural size.)"""
     c = Hh.small_case(P=P, W=64, H=48, seed=30 + P % 7)
     if P >= 8:
         c = _with_depth_ties(c, P // 4)
@@ -428,6 +431,143 @@ def test_parity_depth_sort_tiles(P):
 def test_parity_binning_paths():
     _run(Hh.small_case(P=10000, W=256, H=256, seed=7, log_scale=math.log(0.03)))
     _run(Hh.small_case(P=500, W=100, H=70, seed=2, kernel_size=0.1))
+
+
+def _place(c, idx, px, py, z):
+    """Gaussians `idx` moved to pixel centres (px, py) at depth z (identity camera:
+    pixel = ((ndc + 1) size - 1) / 2)."""
+    f32 = lambda v: torch.as_tensor(np.asarray(v), dtype=torch.float32)  # noqa: E731
+    px, py, z = f32(px), f32(py), f32(z)
+    m = c["inp"]["means3D"].clone()
+    m[idx, 0] = ((2 * px + 1) / c["W"] - 1) * z * c["tanx"]
+    m[idx, 1] = ((2 * py + 1) / c["H"] - 1) * z * c["tany"]
+    m[idx, 2] = z
+    c["inp"]["means3D"] = m.contiguous()
+
+
+def _reshape(c, idx, scale, opacity=0.8):
+    """Gaussians `idx` axis-aligned with scales `scale` (x, y, z) and the given opacity."""
+    s, r, op = (c["inp"][k].clone() for k in ("scales", "rotations", "opacities"))
+    s[idx] = torch.tensor(scale, dtype=torch.float32)
+    r[idx] = torch.tensor([1.0, 0.0, 0.0, 0.0])
+    op[idx] = opacity
+    c["inp"].update(scales=s.contiguous(), rotations=r.contiguous(), opacities=op.contiguous())
+
+
+def _surely_live_tiles(o, g, W, H):
+    """Tiles that Gaussian g certainly keeps after tile culling, from the
+    oracle's geometry: those holding a pixel of the row or the column through
+    its centre with power <= 0 and alpha >= 2/255 (twice the cull's 1/255, so no
+    rounding decides it).  A lower bound of its live tiles; set of (ty, tx)."""
+    geo = o["state"].geometry()
+    mx, my = geo["means2D"][g].astype(np.float64)
+    a, b, cc, op = geo["conic_opacity"][g].astype(np.float64)
+    x0, y0 = int(np.clip(round(mx), 0, W - 1)), int(np.clip(round(my), 0, H - 1))
+    live = set()
+    for xs, ys in ((np.arange(W, dtype=np.float64), np.full(W, float(y0))),
+                   (np.full(H, float(x0)), np.arange(H, dtype=np.float64))):
+        dx, dy = mx - xs, my - ys
+        power = -0.5 * (a * dx * dx + cc * dy * dy) - b * dx * dy
+        ok = (power <= 0) & (op * np.exp(np.minimum(power, 0.0)) >= 2.0 / 255.0)
+        live |= set(zip((ys[ok] // 16).astype(int).tolist(), (xs[ok] // 16).astype(int).tolist()))
+    return live
+
+
+def _gpu_entries_of(out, g, H, W):
+    """How many per-tile list entries of the GPU forward name Gaussian g."""
+    from diff_gaussian_rasterization import _C
+
+    plist, ranges = _C.debug_binning(out[7], out[9], out[0], H, W)
+    return int((plist[:int(ranges[:, 1].max())] == g).sum())
+
+
+def test_parity_binning_coop_emission_16bit():
+    """The instance-sort path (1025 tiles across, 16-bit tile keys) with
+    Gaussians of more than kCoopLive = 32 live tiles: binning.hip's cooperative
+    emission (a wave emits one Gaussian, a tile row per lane), one of them
+    clipped by the right image edge."""
+    W, H = 16400, 40
+    c = Hh.small_case(P=600, W=W, H=H, seed=9, log_scale=math.log(0.01))
+    wide = [5, 6, 7, 8]
+    _place(c, wide, [2000.4, 8200.0, 12001.7, 16395.0], [19.5, 3.0, 36.2, 20.0], [2.5, 3.0, 3.5, 2.2])
+    _reshape(c, wide, [0.05, 0.05, 0.05])
+    out, o, _, _ = _run(c, check_bwd=False)
+    for g in wide:
+        sure = _surely_live_tiles(o, g, W, H)
+        assert o["radii"][g] > 0 and len(sure) > 32, (g, len(sure))
+        assert _gpu_entries_of(out, g, H, W) >= len(sure)
+
+
+def _binning_32bit_case():
+    """W = 16400, H = 1040: 1025 x 65 = 66625 tiles, the smallest grid with more
+    than 1024 tiles on a side and more than 65536 in all.  300 small Gaussians;
+    32 of them moved into tile row 64 and the right end of row 63 (tile ids >=
+    65536), two made thin and taller than the image (more than 64 tile rows),
+    one of those clipped by the right image edge."""
+    W, H = 16400, 1040
+    c = Hh.small_case(P=300, W=W, H=H, seed=61, log_scale=math.log(0.002))
+    rng = np.random.default_rng(61)
+    _place(c, list(range(24)), rng.uniform(100, W - 100, 24), rng.uniform(1026, 1038, 24), rng.uniform(2, 4, 24))
+    _place(c, list(range(24, 32)), rng.uniform(961 * 16 + 40, W - 40, 8), rng.uniform(1010, 1022, 8),
+           rng.uniform(2, 4, 8))
+    tall = [40, 41]
+    _place(c, tall, [3000.3, 16390.0], [519.5, 530.0], [2.0, 2.5])
+    _reshape(c, tall, [0.003, 0.04, 0.003])
+    return c, tall
+
+
+def test_parity_binning_32bit_tile_keys():
+    """The instance-sort path with 32-bit tile keys (emit_keys_kernel<uint32_t>,
+    the 32-bit radix_sort_pairs, tile_ranges_kernel<uint32_t>) and the
+    cooperative emission's second 64-row step.  K, radii and the per-tile
+    lists are checked over the whole grid, as _run does.  The images (0.5 GB,
+    whose full audit alone takes 8 s on the host) are compared on the pixels
+    of every tile with an entry in the GPU's lists plus 512 fixed random other
+    tiles, by _check_image's bars; every pixel of a tile without entries must
+    be exactly the (zero) background on the GPU."""
+    from diff_gaussian_rasterization import _C
+
+    c, tall = _binning_32bit_case()
+    W, H = c["W"], c["H"]
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    assert gx > 1024 and gx * gy > 65536
+    a = _fwd_args(c)
+    o = O.forward(*a)
+    # the scene does what it is for, by the oracle's output
+    orng = o["state"].tile_state()["ranges"].astype(np.int64)
+    ob = o["state"].binning()["point_list"]
+    high = np.flatnonzero(orng[65536:, 1] > orng[65536:, 0]) + 65536
+    in_high = np.unique(np.concatenate([ob[orng[t, 0]:orng[t, 1]] for t in high])) if len(high) else []
+    assert len(in_high) >= 20, len(in_high)
+    for g in tall:
+        sure = _surely_live_tiles(o, g, W, H)
+        assert len(sure) > 32 and len({ty for ty, _ in sure}) > 64, (g, len(sure))
+    out = _C.rasterize_gaussians(*([_gpu(x) for x in a] + [False]))
+    K, color, alpha, normal, mdepth, radii = out[:6]
+    assert K == o["num_rendered"]
+    assert np.array_equal(radii.cpu().numpy(), o["radii"])
+    _check_binning(out, o, H, W)
+    _, ranges = _C.debug_binning(out[7], out[9], K, H, W, with_list=False)
+    has = ranges[:, 1] > ranges[:, 0]
+    assert has[65536:].any()
+    for g in tall:
+        assert _gpu_entries_of(out, g, H, W) > 64
+    # every pixel outside the tiles with entries: exactly the background
+    tile_has = torch.from_numpy(has.reshape(gy, gx)).to(DEV)
+    px_has = tile_has.repeat_interleave(16, 0)[:H].repeat_interleave(16, 1)[:, :W]
+    for t in (color, alpha, normal, mdepth):
+        assert float((t.abs() * (~px_has)).max()) == 0.0
+    # the tiles with entries and 512 of the others, against the oracle
+    others = np.flatnonzero(~has)
+    pick = np.concatenate([np.flatnonzero(has), np.random.default_rng(0).choice(others, 512, replace=False)])
+    py, px = np.mgrid[0:16, 0:16]
+    ys = ((pick // gx)[:, None] * 16 + py.ravel()[None]).ravel()
+    xs = ((pick % gx)[:, None] * 16 + px.ravel()[None]).ravel()
+    keep = (ys < H) & (xs < W)
+    ys, xs = ys[keep], xs[keep]
+    ys_d, xs_d = torch.from_numpy(ys).to(DEV), torch.from_numpy(xs).to(DEV)
+    for name, t in (("color", color), ("alpha", alpha), ("normal", normal), ("mdepth", mdepth)):
+        _check_image(name, t[:, ys_d, xs_d].cpu().numpy(), o[name][:, ys, xs])
 
 
 def test_parity_long_tile_lists():
@@ -1077,7 +1217,7 @@ def test_c3_backward_linearity(c3):
 
 
 def test_c3_depth_sort_paths(c3):
-    """At full C3 (1M depth keys, 245 tiles of the onesweep look-back):
+    """At full C3 (1M depth keys, 163 tiles of the onesweep look-back):
     dsort.hip and rocPRIM's onesweep sort (GSR_OPT_ROCPRIM_DSORT) give the
     same per-tile lists, entry for entry."""
     from diff_gaussian_rasterization import _C
