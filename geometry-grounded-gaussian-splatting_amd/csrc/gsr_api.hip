@@ -7,6 +7,8 @@
 // and size the binning buffer, like the reference's cudaMemcpy at
 // rasterizer_impl.cu:384.  No other host<->device traffic, no device
 // allocation (all scratch comes from the caller's allocation callbacks).
+#include <float.h>
+#include <math.h>
 #include <stdio.h>
 
 #include <mutex>
@@ -1695,6 +1697,200 @@ int gsr_mesh_filter(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn fa
             "mesh filter gather");
     *num_vertices = Vn;
     *num_faces = Fn;
+    return GSR_OK;
+}
+
+int gsr_mesh_sample_points(gsr_alloc_fn point_alloc, void* point_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                           long long V, long long F, const double* vertices, const void* faces, int faces_int64,
+                           double density, long long* num_points, float* stage_ms, void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_points) return fail(GSR_ERR_ARGS, "mesh_sample_points: missing count output");
+    *num_points = 0;
+    if (stage_ms)
+        for (int k = 0; k < 8; k++) stage_ms[k] = 0.f;
+    if (F < 0 || V < 0) return fail(GSR_ERR_ARGS, "mesh_sample_points: negative size");
+    if (!(density > 0.0) || !(density < HUGE_VAL))
+        return fail(GSR_ERR_ARGS, "mesh_sample_points: density must be positive and finite");
+    if (F >= 0x80000000ll || V >= 0x80000000ll)
+        return fail(GSR_ERR_ARGS, "mesh_sample_points: 2^31 or more triangles or vertices");
+    if (F > 0 && V == 0) return fail(GSR_ERR_ARGS, "mesh_sample_points: faces without vertices");
+    if ((V > 0 && !vertices) || (F > 0 && !faces)) return fail(GSR_ERR_ARGS, "mesh_sample_points: missing buffer");
+    if (!point_alloc || !scratch_alloc) return fail(GSR_ERR_ARGS, "mesh_sample_points: missing allocator");
+    if (V == 0) return GSR_OK;
+    const bool is64 = faces_int64 != 0;
+    TetStageTimes times;
+    times.on = stage_ms != nullptr;
+    times.stream = stream;
+
+    unsigned long long S = 0;
+    PointSampleState ss{};
+    if (F > 0) {
+        void* buf = scratch_alloc(scratch_ctx, carve_point_sample(nullptr, F, ss));
+        if (!buf) return fail(GSR_ERR_ALLOC, "mesh_sample_points: scratch allocation failed");
+        carve_point_sample(aligned_base(buf), F, ss);
+        GSR_TRY(times.begin(0), "event");
+        GSR_TRY(launch_sample_count(F, V, vertices, faces, is64, density, ss, stream), "sample count");
+        GSR_TRY(times.end(0), "event");
+        GSR_TRY(times.begin(1), "event");
+        GSR_TRY(launch_sample_scan(F, ss, stream), "sample scan");
+        GSR_TRY(times.end(1), "event");
+        // the one readback: S (two words) and the bad flag
+        ReadbackLease lease;
+        GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+        HostReadback* rb = lease.rb;
+        lease.arm(stream);
+        GSR_TRY(hipMemcpyAsync(rb->pinned, ss.offsets + F, sizeof(uint64_t), hipMemcpyDeviceToHost, stream),
+                "memcpy sample count");
+        GSR_TRY(hipMemcpyAsync(rb->pinned + 2, ss.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+                "memcpy face flag");
+        GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+        lease.recorded();
+        GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+        if (rb->pinned[2])
+            return fail(GSR_ERR_ARGS, "mesh_sample_points: a face names a vertex outside [0, V), or a triangle is "
+                                      "not finite");
+        S = (unsigned long long)rb->pinned[0] | (unsigned long long)rb->pinned[1] << 32;
+        if (S >= (1ull << 38)) return fail(GSR_ERR_ARGS, "mesh_sample_points: 2^38 or more sampled points");
+    }
+    double* out = (double*)point_alloc(point_ctx, ((size_t)V + (size_t)S) * 3 * sizeof(double));
+    if (!out) return fail(GSR_ERR_ALLOC, "mesh_sample_points: points allocation failed");
+    GSR_TRY(times.begin(2), "event");
+    GSR_TRY(hipMemcpyAsync(out, vertices, (size_t)V * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream),
+            "copy vertices");
+    if (S > 0) GSR_TRY(launch_sample_emit(F, V, S, vertices, faces, is64, density, ss, out, stream), "sample emit");
+    GSR_TRY(times.end(2), "event");
+    GSR_TRY(times.collect(stage_ms), "stage times");
+    *num_points = V + (long long)S;
+    return GSR_OK;
+}
+
+int gsr_points_downsample(gsr_alloc_fn kept_alloc, void* kept_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                          long long N, const double* points, double radius, long long* num_kept,
+                          long long* num_rounds, float* stage_ms, void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_kept) return fail(GSR_ERR_ARGS, "points_downsample: missing count output");
+    *num_kept = 0;
+    if (num_rounds) *num_rounds = 0;
+    if (stage_ms)
+        for (int k = 0; k < 8; k++) stage_ms[k] = 0.f;
+    if (N < 0) return fail(GSR_ERR_ARGS, "points_downsample: negative size");
+    if (!(radius > 0.0) || !(radius < HUGE_VAL))
+        return fail(GSR_ERR_ARGS, "points_downsample: radius must be positive and finite");
+    if (N == 0) return GSR_OK;
+    if (N >= 0x80000000ll) return fail(GSR_ERR_ARGS, "points_downsample: 2^31 or more points");
+    if (!points) return fail(GSR_ERR_ARGS, "points_downsample: missing buffer");
+    if (!kept_alloc || !scratch_alloc) return fail(GSR_ERR_ARGS, "points_downsample: missing allocator");
+    TetStageTimes times;
+    times.on = stage_ms != nullptr;
+    times.stream = stream;
+
+    PointThinState ts;
+    void* buf = scratch_alloc(scratch_ctx, carve_point_thin(nullptr, N, ts));
+    if (!buf) return fail(GSR_ERR_ALLOC, "points_downsample: scratch allocation failed");
+    carve_point_thin(aligned_base(buf), N, ts);
+    GSR_TRY(times.begin(0), "event");
+    GSR_TRY(launch_point_bounds(N, points, ts.partials, ts.bounds, stream), "point bounds");
+    GSR_TRY(times.end(0), "event");
+    // first readback: the bounds, which size the grid
+    double bounds[6];
+    GSR_TRY(hipMemcpyAsync(bounds, ts.bounds, sizeof(bounds), hipMemcpyDeviceToHost, stream), "memcpy bounds");
+    GSR_TRY(hipStreamSynchronize(stream), "stream sync");
+    PointGrid grid;
+    if (!point_thin_grid(bounds, radius, grid))
+        return fail(GSR_ERR_ARGS, "points_downsample: points are not finite, or span 2^31 or more cells of side radius");
+    GSR_TRY(times.begin(1), "event");
+    GSR_TRY(launch_point_sort(N, points, grid, ts.keys, ts.keys_sorted, ts.order, ts.sx, ts.sy, ts.sz, ts.state, ts.tmp,
+                              ts.tmp_bytes, stream),
+            "point cell sort");
+    GSR_TRY(times.end(1), "event");
+
+    ReadbackLease lease;
+    GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+    HostReadback* rb = lease.rb;
+    lease.arm(stream);
+    // a round decides at least the lowest undecided rank, so N rounds are the most there can be
+    long long rounds = 0;
+    GSR_TRY(times.begin(2), "event");
+    for (;;) {
+        GSR_TRY(launch_thin_round(ts, grid, radius, stream), "thinning round");
+        rounds++;
+        GSR_TRY(hipMemcpyAsync(rb->pinned, ts.undecided, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+                "memcpy undecided flag");
+        GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+        lease.recorded();
+        GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+        if (!rb->pinned[0]) break;
+        if (rounds > N) return fail(GSR_ERR_HIP, "points_downsample: the rounds did not end");
+    }
+    GSR_TRY(times.end(2), "event");
+    GSR_TRY(times.begin(3), "event");
+    GSR_TRY(launch_thin_plan(ts, stream), "thinning plan");
+    GSR_TRY(times.end(3), "event");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 1, ts.flags + N, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy kept count");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    const long long M = rb->pinned[1];
+    void* kept = kept_alloc(kept_ctx, (size_t)M * sizeof(long long));
+    if (!kept) return fail(GSR_ERR_ALLOC, "points_downsample: kept allocation failed");
+    GSR_TRY(times.begin(4), "event");
+    GSR_TRY(launch_thin_write(ts, (long long*)kept, stream), "thinning write");
+    GSR_TRY(times.end(4), "event");
+    GSR_TRY(times.collect(stage_ms), "stage times");
+    *num_kept = M;
+    if (num_rounds) *num_rounds = rounds;
+    return GSR_OK;
+}
+
+int gsr_points_nearest(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long Q, const double* query, long long R,
+                       const double* ref, double max_dist, double* dist, float* stage_ms, void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (stage_ms)
+        for (int k = 0; k < 8; k++) stage_ms[k] = 0.f;
+    if (Q < 0 || R < 0) return fail(GSR_ERR_ARGS, "points_nearest: negative size");
+    if (!(max_dist > 0.0)) return fail(GSR_ERR_ARGS, "points_nearest: max_dist must be positive");
+    if (Q == 0) return GSR_OK;
+    if (Q >= 0x80000000ll || R >= 0x80000000ll) return fail(GSR_ERR_ARGS, "points_nearest: 2^31 or more points");
+    if (!query || !dist || (R > 0 && !ref)) return fail(GSR_ERR_ARGS, "points_nearest: missing buffer");
+    if (R == 0) {
+        GSR_TRY(launch_nearest_fill(Q, dist, stream), "nearest fill");
+        return GSR_OK;
+    }
+    if (!scratch_alloc) return fail(GSR_ERR_ARGS, "points_nearest: missing allocator");
+    TetStageTimes times;
+    times.on = stage_ms != nullptr;
+    times.stream = stream;
+
+    PointNearestState ns;
+    void* buf = scratch_alloc(scratch_ctx, carve_point_nearest(nullptr, Q, R, ns));
+    if (!buf) return fail(GSR_ERR_ALLOC, "points_nearest: scratch allocation failed");
+    carve_point_nearest(aligned_base(buf), Q, R, ns);
+    GSR_TRY(times.begin(0), "event");
+    GSR_TRY(launch_point_bounds(R, ref, ns.partials, ns.bounds, stream), "ref bounds");
+    GSR_TRY(times.end(0), "event");
+    // the one readback: the bounds of ref, which size the grid
+    double bounds[6];
+    GSR_TRY(hipMemcpyAsync(bounds, ns.bounds, sizeof(bounds), hipMemcpyDeviceToHost, stream), "memcpy bounds");
+    GSR_TRY(hipStreamSynchronize(stream), "stream sync");
+    for (double b : bounds)
+        if (!(b > -DBL_MAX && b < DBL_MAX)) return fail(GSR_ERR_ARGS, "points_nearest: ref is not finite");
+    PointGrid grid;
+    point_nearest_grid(bounds, R, grid);
+    GSR_TRY(times.begin(1), "event");
+    GSR_TRY(launch_point_sort(R, ref, grid, ns.rkeys, ns.rkeys_sorted, ns.rorder, ns.rx, ns.ry, ns.rz, nullptr, ns.tmp,
+                              ns.tmp_bytes, stream),
+            "ref cell sort");
+    GSR_TRY(times.end(1), "event");
+    GSR_TRY(times.begin(2), "event");
+    GSR_TRY(launch_nearest_qsort(Q, query, grid, ns, stream), "query sort");
+    GSR_TRY(times.end(2), "event");
+    GSR_TRY(times.begin(3), "event");
+    GSR_TRY(launch_nearest_search(Q, query, R, grid, ns, max_dist, dist, stream), "nearest search");
+    GSR_TRY(times.end(3), "event");
+    GSR_TRY(times.collect(stage_ms), "stage times");
     return GSR_OK;
 }
 

@@ -331,6 +331,69 @@ hipError_t launch_filter_gather(long long F, long long V, const float* vertices,
                                 const MeshFilterState& s, float* vertices_out, long long* faces_out,
                                 hipStream_t stream);
 
+// point-cloud evaluation (pointeval.hip): mesh sampling, radius thinning, bounded nearest point; float64
+struct PointGrid {      // by value into the kernels
+    double mn[3], mx[3];  // bounds of the gridded points
+    double cs;            // cell side
+    long long nc[3];      // cells per axis
+    int bx, by, bz;       // key = cx << (by + bz) | cy << bz | cz
+    int hashed;           // more than 64 key bits: key = hash of the cell
+};
+struct PointSampleState {
+    uint64_t* offsets;  // [F + 1] samples per triangle, then their exclusive scan: offsets[F] = S
+    uint32_t* bad;      // a face names a vertex outside [0, V), or a non-finite lattice
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct PointThinState {
+    long long N;
+    double* partials;       // bounds reduction
+    double* bounds;         // [6] min xyz, max xyz
+    uint64_t* keys;         // [N] cell keys in input (shuffled) order
+    uint64_t* keys_sorted;  // [N]
+    uint32_t* order;        // [N] the rank (input position) of each sorted point
+    double *sx, *sy, *sz;   // [N] the sorted points
+    uint32_t* state;        // [N] by sorted position: undecided, kept, removed
+    uint32_t* undecided;    // a round left a point undecided
+    uint32_t* flags;        // [N + 1] (over keys) kept by rank, then their exclusive scan: flags[N] = M
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct PointNearestState {
+    double* partials;
+    double* bounds;
+    uint64_t *rkeys, *rkeys_sorted;  // [R] packed cell keys of ref
+    uint32_t* rorder;                // [R]
+    double *rx, *ry, *rz;            // [R] ref in key order
+    uint64_t *qkeys, *qkeys_sorted;  // [Q] Morton codes of the queries' cells
+    uint32_t* qorder;                // [Q]
+    void* tmp;
+    size_t tmp_bytes;
+};
+size_t carve_point_sample(void* base, long long F, PointSampleState& s);
+size_t carve_point_thin(void* base, long long N, PointThinState& s);
+size_t carve_point_nearest(void* base, long long Q, long long R, PointNearestState& s);
+bool point_thin_grid(const double* bounds, double radius, PointGrid& g);
+void point_nearest_grid(const double* bounds, long long R, PointGrid& g);
+hipError_t launch_point_bounds(long long n, const double* pts, double* partials, double* bounds, hipStream_t stream);
+hipError_t launch_point_sort(long long n, const double* pts, const PointGrid& g, uint64_t* keys, uint64_t* keys_sorted,
+                             uint32_t* order, double* sx, double* sy, double* sz, uint32_t* state, void* tmp,
+                             size_t tmp_bytes, hipStream_t stream);
+hipError_t launch_sample_count(long long F, long long V, const double* vertices, const void* faces, bool is64,
+                               double density, const PointSampleState& s, hipStream_t stream);
+hipError_t launch_sample_scan(long long F, const PointSampleState& s, hipStream_t stream);
+hipError_t launch_sample_emit(long long F, long long V, unsigned long long S, const double* vertices,
+                              const void* faces, bool is64, double density, const PointSampleState& s, double* out,
+                              hipStream_t stream);
+hipError_t launch_thin_round(const PointThinState& s, const PointGrid& g, double radius, hipStream_t stream);
+hipError_t launch_thin_plan(const PointThinState& s, hipStream_t stream);
+hipError_t launch_thin_write(const PointThinState& s, long long* kept, hipStream_t stream);
+hipError_t launch_nearest_fill(long long Q, double* out, hipStream_t stream);
+hipError_t launch_nearest_qsort(long long Q, const double* query, const PointGrid& g, const PointNearestState& s,
+                                hipStream_t stream);
+hipError_t launch_nearest_search(long long Q, const double* query, long long R, const PointGrid& g,
+                                 const PointNearestState& s, double max_dist, double* out, hipStream_t stream);
+
 // densify.hip: densify / prune plan and gather, radix-select quantile, 3D filter, opacity reset
 constexpr int kMaxDensifyParams = 16;
 enum : int { kDensifyCopy = 0, kDensifyXyz = 1, kDensifyScaling = 2 };

@@ -586,6 +586,57 @@ int gsr_mesh_filter(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn fa
                     long long* num_faces, void* stream);
 
 /*
+ * Point-cloud evaluation (the reference's dtu_eval/eval.py --mode mesh, which
+ * runs numpy, a process pool and sklearn KD-trees on the CPU), in three calls.
+ * All points are float64 [n,3]; the arithmetic is float64 without contraction,
+ * in the reference's order.  Additive: the ABI version is unchanged.
+ *
+ * gsr_mesh_sample_points (eval.py:48-71): vertices [V,3] float64, faces [F,3]
+ * int32 (faces_int64 == 0) or int64.  Output through point_alloc once its size
+ * is known: points [V + S,3], the vertices first, then per triangle with
+ * area2 = |v1 x v2| > 0, in triangle order, v1 k0 + v2 k1 + p0 for
+ * k0 = (i + .5) / max(n1, 1e-7), k1 = (j + .5) / max(n2, 1e-7), k0 + k1 < 1,
+ * 0 <= i <= n1 (outer), 0 <= j <= n2 (inner), n = floor(l / thr),
+ * thr = density sqrt(l1 l2 / area2).  *num_points = V + S.  scratch_alloc is
+ * called once (8 bytes per triangle plus a scan's temporary).  Limits:
+ * F, V < 2^31, S < 2^38.  A vertex id outside [0, V) or a triangle whose
+ * lattice is not finite fails the call with GSR_ERR_ARGS.  Synchronises
+ * `stream` once (S).  stage_ms: count, scan, emit.
+ *
+ * gsr_points_downsample (eval.py:80-94 after the shuffle): points [N,3] in the
+ * order the reference's loop walks them.  A point survives iff no earlier
+ * surviving point has dx^2 + dy^2 + dz^2 <= radius^2 (exact duplicates
+ * included): the sequential loop's result, computed in parallel rounds that run
+ * until no point is undecided (*num_rounds, may be NULL; a chain of
+ * dependencies costs a round per link).  Output through kept_alloc: the
+ * positions of the survivors [M] int64, ascending; *num_kept = M.
+ * scratch_alloc is called once (48 bytes per point plus the radix sort's
+ * temporary).  Limits: N < 2^31, fewer than 2^31 cells of side radius along an
+ * axis.  Synchronises `stream` once for the bounds, once per round and once
+ * for M.  stage_ms: bounds, cell sort, rounds (host waits included), scan,
+ * write.
+ *
+ * gsr_points_nearest: dist [Q] (the caller's buffer) = the Euclidean distance
+ * from query [Q,3] to the nearest of ref [R,3] where that is < max_dist, else
+ * +inf (all +inf when R == 0).  Exact within max_dist.  scratch_alloc is called
+ * once (44 bytes per ref point, 20 per query, plus the sort's temporary).
+ * Limits: Q, R < 2^31; ref must be finite.  Synchronises `stream` once (the
+ * bounds of ref).  stage_ms: bounds, ref sort, query sort, search.
+ *
+ * stage_ms (host, 8 floats, may be NULL; measurement only, adds
+ * synchronisation) as in gsr_marching_tetrahedra.  Every result is the same
+ * bits on every run.
+ */
+int gsr_mesh_sample_points(gsr_alloc_fn point_alloc, void* point_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                           long long V, long long F, const double* vertices, const void* faces, int faces_int64,
+                           double density, long long* num_points, float* stage_ms, void* stream);
+int gsr_points_downsample(gsr_alloc_fn kept_alloc, void* kept_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                          long long N, const double* points, double radius, long long* num_kept,
+                          long long* num_rounds, float* stage_ms, void* stream);
+int gsr_points_nearest(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long Q, const double* query, long long R,
+                       const double* ref, double max_dist, double* dist, float* stage_ms, void* stream);
+
+/*
  * Per-stage GPU timing (no reference equivalent; SURVEY §5 "tracing").  While
  * enabled, every kernel stage of the calls above is bracketed by two hipEvents
  * on the call's stream.  gsr_timing_collect() waits for the recorded events,
