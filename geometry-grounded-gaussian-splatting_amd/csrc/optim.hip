@@ -126,7 +126,9 @@ __global__ void __launch_bounds__(256)
     if (!(r > 0)) return;
     const float gx = vgrad[3 * i], gy = vgrad[3 * i + 1], gz = vgrad[3 * i + 2];
     max_radii2D[i] = fmaxf(max_radii2D[i], (float)r);
-    accum[i] += sqrtf(gx * gx + gy * gy);
+    // torch.norm's order: the squares accumulated left to right, each step one fused multiply-add.  Left to the
+    // compiler's contraction (x fused, y rounded) the norm is 1 ulp off torch's for 1 in 9 Gaussians, 2 ulps in the sum
+    accum[i] += sqrtf(fmaf(gy, gy, gx * gx));
     accum_abs[i] += fabsf(gz);
     denom[i] += 1.f;
 }

@@ -62,7 +62,7 @@ def record_margins(fields: dict, what: str = "") -> None:
     import os
     if not fields:
         return
-    test = os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0]
+    test = os.environ.get("PYTEST_CURRENT_TEST", "").rsplit(" ", 1)[0]  # (drops " (call)"; an id may hold spaces)
     worst = max(fields, key=lambda k: fields[k][0] / fields[k][1])
     v, bar = fields[worst]
     print(f"[margin] {test} {what}: worst {worst} {v:.3e} against {bar:.0e} ({bar / max(v, 1e-300):.1f}x headroom)")
@@ -76,6 +76,58 @@ def record_margins(fields: dict, what: str = "") -> None:
                                 "fields": {k: [float(a), float(b)] for k, (a, b) in fields.items()}}) + "\n")
     except OSError:
         pass
+
+
+def max_err(a, ref) -> float:
+    """max|a-ref| over the elements / max|ref| of the tensor; the absolute
+    max|a-ref| where the reference is all zero (or empty: 0)."""
+    a = torch.as_tensor(a).detach().cpu().double()
+    ref = torch.as_tensor(ref).detach().cpu().double()
+    if ref.numel() == 0:
+        return 0.0
+    num, den = float((a - ref).abs().max()), float(ref.abs().max())
+    return num if den == 0.0 else num / den
+
+
+def row_errs(a, ref) -> torch.Tensor:
+    """max_err row by row (dim 0): max|a-ref| over a row's elements / max|ref|
+    of that row, absolute where the row's reference is zero.  [len(ref)] float64;
+    a non-finite element of `a` gives that row inf."""
+    if torch.as_tensor(ref).numel() == 0:
+        return torch.zeros(len(ref), dtype=torch.float64)
+    a = torch.as_tensor(a).detach().cpu().double().reshape(len(ref), -1)
+    ref = torch.as_tensor(ref).detach().cpu().double().reshape(len(ref), -1)
+    num, den = (a - ref).abs().amax(dim=1), ref.abs().amax(dim=1)
+    e = torch.where(den == 0.0, num, num / den.clamp_min(1e-300))
+    return torch.where(torch.isfinite(a).all(dim=1), e, torch.full_like(e, float("inf")))
+
+
+def row_err(a, ref) -> float:
+    """The worst row of row_errs, so that a wrong row is not diluted by the
+    largest row of the tensor."""
+    e = row_errs(a, ref)
+    return float(e.max()) if e.numel() else 0.0
+
+
+class Yardstick:
+    """The project's float64 yardstick: a GPU result may be no further from
+    the exact float64 value than twice the error of the reference's own fp32
+    arithmetic, e_gpu <= 2 e_fp32 + floor (`floor`: the measured e_gpu where
+    the fp32 reference happens to be exact, rounded up to a power of ten).
+    add() prints every figure; check() records the margins and asserts."""
+
+    def __init__(self, what: str = ""):
+        self.what, self.fields = what, {}
+
+    def add(self, name: str, e_gpu: float, e_fp32: float, floor: float) -> None:
+        assert math.isfinite(e_gpu) and math.isfinite(e_fp32), (name, e_gpu, e_fp32)  # an infinite bar checks nothing
+        print(f"[yard] {self.what} {name}: e_gpu {e_gpu:.3e} e_fp32 {e_fp32:.3e} floor {floor:.0e}")
+        self.fields[name] = (float(e_gpu), 2.0 * float(e_fp32) + floor)
+
+    def check(self) -> None:
+        record_margins({k: v for k, v in self.fields.items() if v[1] > 0.0}, self.what)  # (bar 0: exact, no margin)
+        bad = {k: v for k, v in self.fields.items() if not v[0] <= v[1]}
+        assert not bad, bad
 
 
 def frac_bad(a, b, rtol, atol) -> float:
