@@ -2,8 +2,8 @@
 the C oracle's restatement of warp_patch_ncc_impl.cu (itself pinned to a
 float64 autograd restatement in tests/test_oracle.py).
 
-Tolerances, over the points both call valid (valid flags equal except warps
-within float noise of the image margin, <= 0.2%): the GPU's relative L2
+Tolerances, over the points both call valid (valid flags equal to the float64
+reference's except at measured ties, tests/ncc_ref.py): the GPU's relative L2
 error against the exact (float64 autograd) values is at most twice the
 oracle's, i.e. the HIP kernel is as accurate as the reference's own fp32
 arithmetic; and GPU vs oracle: NCC <= 1e-4, gradients <= 2e-3 relative L2.
@@ -20,6 +20,8 @@ import pytest
 import torch
 
 import helpers as Hh
+import ncc_cases as NC
+import ncc_ref as NR
 from oracle import gsr_oracle as O
 import torch_ref as R_
 from test_oracle import ncc_case
@@ -38,7 +40,13 @@ def test_ncc_parity(P, seed, size):
     ncc, gd, gn, valid = W._C.warp_patch_ncc(d.to(DEV), n.to(DEV), uv.to(DEV), R.reshape(3, 3).to(DEV), T.to(DEV),
                                              ir.to(DEV), inn.to(DEV), *K.values(), False)
     v = valid.cpu().numpy()
-    assert (v != o["valid"]).mean() <= 2e-3  # warps landing within float noise of the image margin
+    # valid is the float64 reference's except at measured ties (tests/test_gpu_ncc_edges.py: a decision within
+    # four times the oracle's own farthest flip of its boundary).  NC.bands() builds every edge case of that file
+    # on the CPU (60,000 candidates, 24 bisection passes: ~3 s), once per process.
+    ref = NR.warp_patch_ncc(d, n, uv, R, T, ir, inn, *K.values())
+    band_m, band_g, _, _ = NC.bands()
+    far = (v != ref["valid"]) & ~NR.ties(ref, band_m, band_g)
+    assert not far.any(), np.flatnonzero(far)[:10]
     both = v & o["valid"]
     if P > 10:
         assert both.sum() > 0.3 * P
