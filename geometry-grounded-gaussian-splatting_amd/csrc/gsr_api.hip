@@ -1700,6 +1700,173 @@ int gsr_mesh_filter(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn fa
     return GSR_OK;
 }
 
+namespace {
+const char* tsdf_camera(const float* intrinsic, const float* extrinsic, TsdfCamera& cam) {
+    if (!intrinsic || !extrinsic) return "missing camera";
+    cam.fx = intrinsic[0], cam.fy = intrinsic[1], cam.cx = intrinsic[2], cam.cy = intrinsic[3];
+    if (!(cam.fx > 0.f) || !(cam.fy > 0.f)) return "focal lengths must be positive";
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) cam.e[r][c] = extrinsic[4 * r + c];
+    return nullptr;
+}
+}  // namespace
+
+int gsr_tsdf_touch(gsr_alloc_fn coord_alloc, void* coord_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                   const float* depth, int H, int W, const float* intrinsic, const float* extrinsic,
+                   float depth_scale, float depth_max, float sdf_trunc, float block_size, long long* num_blocks,
+                   void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_blocks) return fail(GSR_ERR_ARGS, "tsdf_touch: missing count output");
+    *num_blocks = 0;
+    if (H <= 0 || W <= 0 || !depth) return fail(GSR_ERR_ARGS, "tsdf_touch: missing depth image");
+    if ((long long)H * W > 0x40000000ll) return fail(GSR_ERR_ARGS, "tsdf_touch: more than 2^30 pixels");
+    if (!(depth_scale > 0.f) || !(depth_max > 0.f) || !(sdf_trunc > 0.f) || !(block_size > 0.f))
+        return fail(GSR_ERR_ARGS, "tsdf_touch: depth_scale, depth_max, sdf_trunc and block_size must be positive");
+    if (!coord_alloc || !scratch_alloc) return fail(GSR_ERR_ARGS, "tsdf_touch: missing allocator");
+    TsdfCamera cam;
+    if (const char* msg = tsdf_camera(intrinsic, extrinsic, cam)) return fail(GSR_ERR_ARGS, msg);
+
+    TsdfTouchState ts;
+    void* buf = scratch_alloc(scratch_ctx, carve_tsdf_touch(nullptr, H, W, ts));
+    if (!buf) return fail(GSR_ERR_ALLOC, "tsdf_touch: scratch allocation failed");
+    carve_tsdf_touch(aligned_base(buf), H, W, ts);
+    GSR_TRY(launch_tsdf_touch(H, W, depth, cam, depth_scale, depth_max, sdf_trunc, block_size, ts, stream),
+            "tsdf touch");
+
+    // the one readback: the number of blocks and the out-of-range flag
+    ReadbackLease lease;
+    GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+    HostReadback* rb = lease.rb;
+    lease.arm(stream);
+    GSR_TRY(hipMemcpyAsync(rb->pinned, ts.heads + ts.n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy block count");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 1, ts.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy range flag");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    lease.recorded();
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    if (rb->pinned[1]) return fail(GSR_ERR_ARGS, "tsdf_touch: a sample falls in a block beyond +-2^20");
+    const long long n = rb->pinned[0];
+    if (n == 0) return GSR_OK;
+    void* coords = coord_alloc(coord_ctx, (size_t)n * 3 * sizeof(int));
+    if (!coords) return fail(GSR_ERR_ALLOC, "tsdf_touch: block coordinate allocation failed");
+    GSR_TRY(launch_tsdf_touch_write(ts, (int*)coords, stream), "tsdf touch write");
+    *num_blocks = n;
+    return GSR_OK;
+}
+
+int gsr_tsdf_lookup(long long n, const int* block_coords, long long num_blocks, const long long* sorted_keys,
+                    int* rank, void* stream_ptr) {
+    if (n < 0 || num_blocks < 0 || num_blocks > 0x7fffffffll) return fail(GSR_ERR_ARGS, "tsdf_lookup: invalid size");
+    if (n == 0) return GSR_OK;
+    if (!block_coords || !rank || (num_blocks > 0 && !sorted_keys))
+        return fail(GSR_ERR_ARGS, "tsdf_lookup: missing buffer");
+    hipError_t e = launch_tsdf_lookup(n, block_coords, (int)num_blocks, (const uint64_t*)sorted_keys, rank,
+                                      (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "tsdf lookup", e);
+}
+
+int gsr_tsdf_integrate(long long n, int block_resolution, const int* block_coords, const int* slots,
+                       long long capacity, float voxel_size, float* tsdf, float* weight, float* color,
+                       const float* depth, const float* image, int H, int W, const float* intrinsic,
+                       const float* extrinsic, float depth_scale, float depth_max, float sdf_trunc,
+                       void* stream_ptr) {
+    if (n < 0 || n > 0x7fffffffll || capacity < 0 || capacity > 0x7fffffffll)
+        return fail(GSR_ERR_ARGS, "tsdf_integrate: invalid size");
+    if (block_resolution != 8 && block_resolution != 16)
+        return fail(GSR_ERR_ARGS, "tsdf_integrate: block_resolution must be 8 or 16");
+    if (H <= 0 || W <= 0 || !depth) return fail(GSR_ERR_ARGS, "tsdf_integrate: missing depth image");
+    if ((long long)H * W > 0x40000000ll) return fail(GSR_ERR_ARGS, "tsdf_integrate: more than 2^30 pixels");
+    if (!(voxel_size > 0.f) || !(depth_scale > 0.f) || !(depth_max > 0.f) || !(sdf_trunc > 0.f))
+        return fail(GSR_ERR_ARGS, "tsdf_integrate: voxel_size, depth_scale, depth_max and sdf_trunc must be positive");
+    if ((color != nullptr) != (image != nullptr))
+        return fail(GSR_ERR_ARGS, "tsdf_integrate: a colour grid needs a colour image and the reverse");
+    TsdfCamera cam;
+    if (const char* msg = tsdf_camera(intrinsic, extrinsic, cam)) return fail(GSR_ERR_ARGS, msg);
+    if (n == 0) return GSR_OK;
+    if (!block_coords || !slots || !tsdf || !weight) return fail(GSR_ERR_ARGS, "tsdf_integrate: missing buffer");
+    hipError_t e = launch_tsdf_integrate((int)n, block_resolution, block_coords, slots, capacity, voxel_size, tsdf,
+                                         weight, color, depth, image, H, W, cam, depth_scale, depth_max, sdf_trunc,
+                                         (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "tsdf integrate", e);
+}
+
+int gsr_tsdf_extract(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn color_alloc, void* color_ctx,
+                     gsr_alloc_fn face_alloc, void* face_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                     long long num_blocks, int block_resolution, float voxel_size, float weight_threshold,
+                     const long long* sorted_keys, const int* sorted_slots, const float* tsdf, const float* weight,
+                     const float* color, long long* num_vertices, long long* num_faces, float* stage_ms,
+                     void* stream_ptr) {
+    constexpr int debug = 0;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (!num_vertices || !num_faces) return fail(GSR_ERR_ARGS, "tsdf_extract: missing count outputs");
+    *num_vertices = *num_faces = 0;
+    if (stage_ms)
+        for (int k = 0; k < 8; k++) stage_ms[k] = 0.f;
+    if (num_blocks < 0) return fail(GSR_ERR_ARGS, "tsdf_extract: negative size");
+    if (block_resolution != 8 && block_resolution != 16)
+        return fail(GSR_ERR_ARGS, "tsdf_extract: block_resolution must be 8 or 16");
+    if (!(voxel_size > 0.f)) return fail(GSR_ERR_ARGS, "tsdf_extract: voxel_size must be positive");
+    if (num_blocks == 0) return GSR_OK;
+    // 5 triangles per voxel at most: the per-block totals stay below 2^32 over all blocks
+    if (num_blocks * block_resolution * block_resolution * block_resolution > 0x7fffffffll / 5)
+        return fail(GSR_ERR_ARGS, "tsdf_extract: more than (2^31 - 1) / 5 voxels");
+    if (!sorted_keys || !sorted_slots || !tsdf || !weight) return fail(GSR_ERR_ARGS, "tsdf_extract: missing buffer");
+    if (!vertex_alloc || !face_alloc || !scratch_alloc || (color && !color_alloc))
+        return fail(GSR_ERR_ARGS, "tsdf_extract: missing allocator");
+    const uint64_t* keys = (const uint64_t*)sorted_keys;
+    TetStageTimes times;
+    times.on = stage_ms != nullptr;
+    times.stream = stream;
+
+    TsdfExtractState es;
+    void* buf = scratch_alloc(scratch_ctx, carve_tsdf_extract(nullptr, (int)num_blocks, block_resolution, es));
+    if (!buf) return fail(GSR_ERR_ALLOC, "tsdf_extract: scratch allocation failed");
+    carve_tsdf_extract(aligned_base(buf), (int)num_blocks, block_resolution, es);
+    GSR_TRY(times.begin(0), "event");
+    GSR_TRY(launch_mc_mark(keys, sorted_slots, tsdf, weight, weight_threshold, es, stream), "marching cubes mark");
+    GSR_TRY(times.end(0), "event");
+    GSR_TRY(times.begin(1), "event");
+    GSR_TRY(launch_mc_count(es, stream), "marching cubes count");
+    GSR_TRY(times.end(1), "event");
+
+    // the one readback: V and F
+    ReadbackLease lease;
+    GSR_TRY(g_readback_pool.acquire(lease.rb), "pinned readback buffer");
+    HostReadback* rb = lease.rb;
+    lease.arm(stream);
+    GSR_TRY(hipMemcpyAsync(rb->pinned, es.vbase + num_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy vertex count");
+    GSR_TRY(hipMemcpyAsync(rb->pinned + 1, es.fbase + num_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+            "memcpy face count");
+    GSR_TRY(hipEventRecord(rb->ev, stream), "event record");
+    lease.recorded();
+    GSR_TRY(hipEventSynchronize(rb->ev), "event sync");
+    const long long V = rb->pinned[0], F = rb->pinned[1];
+    if (F == 0) {  // a vertex exists only on an emitted cube's crossed edge, and such a cube has a triangle
+        GSR_TRY(times.collect(stage_ms), "stage times");
+        return GSR_OK;
+    }
+    void* vout = vertex_alloc(vertex_ctx, (size_t)V * 3 * sizeof(float));
+    if (!vout) return fail(GSR_ERR_ALLOC, "tsdf_extract: vertices allocation failed");
+    void* cout = color ? color_alloc(color_ctx, (size_t)V * 3 * sizeof(float)) : nullptr;
+    if (color && !cout) return fail(GSR_ERR_ALLOC, "tsdf_extract: colours allocation failed");
+    void* fout = face_alloc(face_ctx, (size_t)F * 3 * sizeof(long long));
+    if (!fout) return fail(GSR_ERR_ALLOC, "tsdf_extract: faces allocation failed");
+    GSR_TRY(times.begin(2), "event");
+    GSR_TRY(launch_mc_vertices(keys, sorted_slots, tsdf, color, voxel_size, es, (float*)vout, (float*)cout, stream),
+            "marching cubes vertices");
+    GSR_TRY(times.end(2), "event");
+    GSR_TRY(times.begin(3), "event");
+    GSR_TRY(launch_mc_faces(keys, es, (long long*)fout, stream), "marching cubes faces");
+    GSR_TRY(times.end(3), "event");
+    GSR_TRY(times.collect(stage_ms), "stage times");
+    *num_vertices = V;
+    *num_faces = F;
+    return GSR_OK;
+}
+
 int gsr_mesh_sample_points(gsr_alloc_fn point_alloc, void* point_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
                            long long V, long long F, const double* vertices, const void* faces, int faces_int64,
                            double density, long long* num_points, float* stage_ms, void* stream_ptr) {

@@ -331,6 +331,52 @@ hipError_t launch_filter_gather(long long F, long long V, const float* vertices,
                                 const MeshFilterState& s, float* vertices_out, long long* faces_out,
                                 hipStream_t stream);
 
+// TSDF fusion and marching cubes (tsdf.hip).  Touch: 20 bytes per sample (4 per stride-4 pixel) plus
+// the sort's temporary.  Extract: 3.5 bytes per voxel (case, 4 mask bits, vertex offset) and 8 per block.
+struct TsdfCamera {  // by value into the kernels
+    float fx, fy, cx, cy;
+    float e[3][4];  // the first three rows of the world -> camera matrix
+};
+struct TsdfTouchState {
+    int gw, gh;             // stride-4 lattice
+    long long n;            // 4 gw gh samples
+    uint64_t* keys;         // [n] packed block keys, all ones where there is no sample
+    uint64_t* keys_sorted;  // [n]
+    uint32_t* heads;        // [n + 1] run heads, then their exclusive scan: heads[n] = the number of blocks
+    uint32_t* bad;          // a sample beyond +-2^20 blocks
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct TsdfExtractState {
+    int nb, R;
+    uint8_t* cases;     // [nb R^3] the case of every emitted cube, 0 otherwise
+    uint32_t* masks;    // [nb R^3 / 8] 4 bits per voxel: its x, y, z edge carries a vertex
+    uint16_t* voffset;  // [nb R^3] vertices of the block before the voxel's
+    uint32_t* vbase;    // [nb + 1] vertices per block, then their exclusive scan
+    uint32_t* fbase;    // [nb + 1] the same for triangles
+    void* tmp;
+    size_t tmp_bytes;
+};
+size_t carve_tsdf_touch(void* base, int H, int W, TsdfTouchState& s);
+size_t carve_tsdf_extract(void* base, int nb, int R, TsdfExtractState& s);
+hipError_t launch_tsdf_touch(int H, int W, const float* depth, const TsdfCamera& cam, float depth_scale,
+                             float depth_max, float trunc, float block_size, const TsdfTouchState& s,
+                             hipStream_t stream);
+hipError_t launch_tsdf_touch_write(const TsdfTouchState& s, int* coords, hipStream_t stream);
+hipError_t launch_tsdf_lookup(long long n, const int* coords, int nb, const uint64_t* sorted_keys, int* rank,
+                              hipStream_t stream);
+hipError_t launch_tsdf_integrate(int n, int R, const int* coords, const int* slots, long long capacity,
+                                 float voxel_size, float* tsdf, float* weight, float* color, const float* depth,
+                                 const float* image, int H, int W, const TsdfCamera& cam, float depth_scale,
+                                 float depth_max, float trunc, hipStream_t stream);
+hipError_t launch_mc_mark(const uint64_t* keys, const int* slots, const float* tsdf, const float* weight,
+                          float threshold, const TsdfExtractState& s, hipStream_t stream);
+hipError_t launch_mc_count(const TsdfExtractState& s, hipStream_t stream);
+hipError_t launch_mc_vertices(const uint64_t* keys, const int* slots, const float* tsdf, const float* color,
+                              float voxel_size, const TsdfExtractState& s, float* vertices, float* colors,
+                              hipStream_t stream);
+hipError_t launch_mc_faces(const uint64_t* keys, const TsdfExtractState& s, long long* faces, hipStream_t stream);
+
 // point-cloud evaluation (pointeval.hip): mesh sampling, radius thinning, bounded nearest point; float64
 struct PointGrid {      // by value into the kernels
     double mn[3], mx[3];  // bounds of the gridded points

@@ -10,6 +10,11 @@ gsr_mesh_filter, csrc/meshclean.hip).
     write_ply("recon.ply", vertices, faces)
     write_ply("recon_post.ply", *post_process_mesh(vertices, faces, cluster_to_keep=1))
 
+and the TSDF path of the DTU script (mesh_extract.py:40-89; gsr_tsdf, csrc/tsdf.hip):
+
+    vertices, faces, colors = extract_mesh_tsdf(views, pc, pipe, background, kernel_size)
+    write_ply("recon.ply", vertices, faces, colors)
+
 Face order: a tet's one or two triangles sit next to each other, in tet
 order.  The reference lists, chunk by chunk, the one-triangle tets before the
 two-triangle tets; the mesh is the same set of oriented triangles.
@@ -331,17 +336,81 @@ def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_bi
     return vertices, faces
 
 
-def write_ply(path, vertices, faces):
-    """A binary little-endian PLY of float32 vertices [N,3] and triangles [M,3]."""
+def _view_camera(view):
+    """(fx, fy, cx, cy) and the 4x4 world -> camera matrix of a view (mesh_extract.py:79-81); a view
+    without Fx / Fy / Cx / Cy gets them from its field of view, the principal point at the centre."""
+    import math
+
+    W, H = view.image_width, view.image_height
+    fx = getattr(view, "Fx", None) or W / (2.0 * math.tan(view.FoVx * 0.5))
+    fy = getattr(view, "Fy", None) or H / (2.0 * math.tan(view.FoVy * 0.5))
+    cx = getattr(view, "Cx", None)
+    cy = getattr(view, "Cy", None)
+    cx = (W - 1) * 0.5 if cx is None else cx
+    cy = (H - 1) * 0.5 if cy is None else cy
+    return (float(fx), float(fy), float(cx), float(cy)), view.world_view_transform.T
+
+
+@torch.no_grad()
+def extract_mesh_tsdf(views, pc, pipe, background, kernel_size, voxel_size=0.002, cluster_to_keep=None,
+                      block_resolution=16, depth_scale=1.0, depth_max=8.0, trunc_voxel_multiplier=8.0,
+                      weight_threshold=3.0):
+    """mesh_extract.py:40-89 on the device: every view is rendered, its colour
+    clamped to [0,1], its median depth zeroed where gt_mask < 0.5, and fused
+    into a gsr_tsdf.VoxelBlockGrid (touch, then integrate); marching cubes
+    once at the end.  -> (vertices [V,3] float32, faces [F,3] int64, colors
+    [V,3] float32): recon.ply.  With an integer `cluster_to_keep` also the
+    post_process_mesh result: (vertices, faces, colors, (vertices_post,
+    faces_post)), the geometry of recon_post.ply."""
+    from gaussian_renderer import render
+    from gsr_tsdf import VoxelBlockGrid
+
+    vbg = None
+    for view in views:
+        pkg = render(view, pc, pipe, background, kernel_size)
+        color = torch.clamp(pkg["render"], min=0, max=1.0).permute(1, 2, 0).contiguous()
+        depth = pkg["median_depth"].clone()
+        mask = getattr(view, "gt_mask", None)
+        if mask is not None:
+            depth[mask < 0.5] = 0
+        depth = depth[0].contiguous()
+        if vbg is None:
+            vbg = VoxelBlockGrid(voxel_size, block_resolution, with_color=True, device=depth.device)
+        intrinsic, extrinsic = _view_camera(view)
+        blocks = vbg.compute_unique_block_coordinates(depth, intrinsic, extrinsic, depth_scale, depth_max,
+                                                      trunc_voxel_multiplier)
+        vbg.integrate(blocks, depth, color, intrinsic, extrinsic, depth_scale, depth_max, trunc_voxel_multiplier)
+    if vbg is None:
+        raise ValueError("extract_mesh_tsdf: no views")
+    vertices, faces, colors = vbg.extract_triangle_mesh(weight_threshold)
+    if cluster_to_keep is not None:
+        return vertices, faces, colors, post_process_mesh(vertices, faces, cluster_to_keep)
+    return vertices, faces, colors
+
+
+def write_ply(path, vertices, faces, colors=None):
+    """A binary little-endian PLY of float32 vertices [N,3] and triangles [M,3]; with `colors` [N,3]
+    in [0,1], uchar red / green / blue per vertex as well."""
     v = np.ascontiguousarray(torch.as_tensor(vertices).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
     f = torch.as_tensor(faces).detach().cpu().numpy().reshape(-1, 3)
     rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
     rec["n"] = 3
     rec["v"] = f
+    vertex_props = "property float x\nproperty float y\nproperty float z\n"
+    vertex_bytes = v.tobytes()
+    if colors is not None:
+        c = torch.as_tensor(colors).detach().cpu().numpy().reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply: {c.shape[0]} colours for {v.shape[0]} vertices")
+        vrec = np.empty(v.shape[0], dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+        vrec["p"] = v
+        vrec["c"] = np.clip(np.rint(c.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+        vertex_props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        vertex_bytes = vrec.tobytes()
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {v.shape[0]}\n{vertex_props}"
               f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))
-        fh.write(v.tobytes())
+        fh.write(vertex_bytes)
         fh.write(rec.tobytes())

@@ -586,6 +586,73 @@ int gsr_mesh_filter(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn fa
                     long long* num_faces, void* stream);
 
 /*
+ * TSDF fusion and marching cubes (the open3d VoxelBlockGrid of the
+ * reference's mesh_extract.py:63-85, which runs on the CPU).  Additive: the
+ * ABI version is unchanged.  The contract is DESIGN §6h; it restates open3d's
+ * behaviour from memory and claims no bit-parity with it.  Blocks are R^3
+ * voxels (block_resolution R = 8 or 16); a voxel is linear in (z R + y) R + x;
+ * a block's key is (x + 2^20) << 42 | (y + 2^20) << 21 | (z + 2^20).  The
+ * caller owns the grid: tsdf / weight [capacity, R^3] fp32, colour
+ * [capacity, R^3, 3] fp32 or NULL, and the index sorted_keys [num_blocks]
+ * (ascending) with sorted_slots [num_blocks].  intrinsic (fx, fy, cx, cy) and
+ * extrinsic (world -> camera, 4x4 row-major) are host fp32; all device
+ * arithmetic is fp32.
+ *
+ * gsr_tsdf_touch: the blocks a depth image [H,W] touches.  Every pixel with
+ * x % 4 == y % 4 == 0 and 0 < d = depth / depth_scale < depth_max gives four
+ * samples o + t dir, t = t_min + k (t_max - t_min) / 3, t_min = max(d -
+ * sdf_trunc, 0), t_max = min(d + sdf_trunc, depth_max), o = -R^T t the camera
+ * centre, dir = R^T ((x - cx) / fx, (y - cy) / fy, 1); block =
+ * floor(sample / block_size).  Output through coord_alloc (not called for 0):
+ * the distinct blocks [n,3] int32, ascending by key.  A block beyond +-2^20
+ * fails the call with GSR_ERR_ARGS.  scratch_alloc is called once (20 bytes
+ * per sample plus the sort's temporary).  Synchronises `stream` once (n).
+ *
+ * gsr_tsdf_lookup: rank [n] int32 = the position of each of block_coords [n,3]
+ * in sorted_keys, or -1.  No synchronisation.
+ *
+ * gsr_tsdf_integrate: one view into the listed blocks only (block_coords
+ * [n,3] int32 with their slots [n] int32; a slot outside [0, capacity) is
+ * skipped).  Per voxel: camera-space position of (block R + (x, y, z))
+ * voxel_size; skipped when z_c <= 0, when the pixel (round(fx x_c / z_c + cx),
+ * round(fy y_c / z_c + cy)) is outside the image, when d = depth / depth_scale
+ * is not in (0, depth_max], or when d - z_c < -sdf_trunc; else the running
+ * mean of min(d - z_c, sdf_trunc) / sdf_trunc (and of image [H,W,3]) with
+ * weight + 1.  One thread owns a voxel; a block must not be listed twice.  No
+ * synchronisation.
+ *
+ * gsr_tsdf_extract: marching cubes over the cubes whose 8 corners lie in
+ * present blocks with weight > weight_threshold; inside is tsdf < 0.  One
+ * vertex per crossed edge of an emitted cube, shared by the cubes around it,
+ * at (p_a + t (p_b - p_a)) voxel_size, t = tsdf_a / (tsdf_a - tsdf_b), colour
+ * likewise.  Vertices are ordered by (block in key order, voxel, axis),
+ * triangles by (block, voxel, order in the case table of csrc/mc_table.h);
+ * normals point to the positive side.  Outputs through the callbacks (not
+ * called when there is no triangle): vertices [V,3] fp32, colours [V,3] fp32
+ * (only with color), faces [F,3] int64.  scratch_alloc is called once (3.5
+ * bytes per voxel).  Limit: fewer than (2^31 - 1) / 5 voxels.  Synchronises
+ * `stream` once (V and F).  stage_ms (host, 8 floats, may be NULL;
+ * measurement only, adds synchronisation): mark, count, vertices, faces.  The
+ * result is the same bits on every run.
+ */
+int gsr_tsdf_touch(gsr_alloc_fn coord_alloc, void* coord_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                   const float* depth, int H, int W, const float* intrinsic, const float* extrinsic,
+                   float depth_scale, float depth_max, float sdf_trunc, float block_size, long long* num_blocks,
+                   void* stream);
+int gsr_tsdf_lookup(long long n, const int* block_coords, long long num_blocks, const long long* sorted_keys,
+                    int* rank, void* stream);
+int gsr_tsdf_integrate(long long n, int block_resolution, const int* block_coords, const int* slots,
+                       long long capacity, float voxel_size, float* tsdf, float* weight, float* color,
+                       const float* depth, const float* image, int H, int W, const float* intrinsic,
+                       const float* extrinsic, float depth_scale, float depth_max, float sdf_trunc, void* stream);
+int gsr_tsdf_extract(gsr_alloc_fn vertex_alloc, void* vertex_ctx, gsr_alloc_fn color_alloc, void* color_ctx,
+                     gsr_alloc_fn face_alloc, void* face_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                     long long num_blocks, int block_resolution, float voxel_size, float weight_threshold,
+                     const long long* sorted_keys, const int* sorted_slots, const float* tsdf, const float* weight,
+                     const float* color, long long* num_vertices, long long* num_faces, float* stage_ms,
+                     void* stream);
+
+/*
  * Point-cloud evaluation (the reference's dtu_eval/eval.py --mode mesh, which
  * runs numpy, a process pool and sklearn KD-trees on the CPU), in three calls.
  * All points are float64 [n,3]; the arithmetic is float64 without contraction,
