@@ -1,5 +1,6 @@
 // gsr_kernels.h — internal launch interface between the C-ABI host code
-// (gsr_api.hip) and the kernels.  Not part of the public ABI (include/gsr.h).
+// (gsr_api.hip for the rasteriser, api_train.hip, api_mesh.hip, api_eval.hip) and
+// the kernels.  Not part of the public ABI (include/gsr.h).
 #pragma once
 
 #include "gsr_common.h"
