@@ -422,6 +422,30 @@ int gsr_debug_depth_sort(int P, const uint32_t* keys, uint32_t* keys_sorted, uin
     return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug depth sort", e);
 }
 
+int gsr_debug_list_constants(int* out, int n) {
+    if (n < 0 || (n > 0 && !out)) return -1;
+    return gsr::list_constants(out, n);
+}
+
+// (cap + kScanTile must fit the kernels' 32-bit indices)
+static bool scan_cap_ok(long long cap) { return cap >= 0 && cap <= 0x7fffffffLL; }
+
+long long gsr_debug_scan_excl_bytes(long long cap) {
+    if (!scan_cap_ok(cap)) return -1;
+    return (long long)sizeof(uint32_t) * gsr::scan_sums_count((size_t)cap);
+}
+
+int gsr_debug_scan_excl(const uint32_t* in, uint32_t* out, long long cap, uint32_t n_host, const uint32_t* n_dev,
+                        uint32_t mul, void* sums, void* stream_ptr) {
+    if (!scan_cap_ok(cap) || !out || !sums || (cap > 0 && !in)) return fail(GSR_ERR_ARGS, "invalid arguments");
+    if ((uintptr_t)in % 16) return fail(GSR_ERR_ARGS, "scan input must be 16-byte aligned");
+    if ((uintptr_t)out % 4 || (uintptr_t)sums % 4) return fail(GSR_ERR_ARGS, "scan output and sums must be 4-byte aligned");
+    if (!n_dev && (long long)n_host > cap) return fail(GSR_ERR_ARGS, "scan length above its bound");
+    hipError_t e = gsr::launch_scan_excl(in, out, (size_t)cap, n_host, n_dev, mul, reinterpret_cast<uint32_t*>(sums),
+                                         (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug scan", e);
+}
+
 int gsr_set_option(int opt, int value) {
     if (opt < 0 || opt >= gsr::kNumOptions || gsr::option_retired(opt)) return fail(GSR_ERR_ARGS, "unknown option");
     gsr::g_options[opt] = value;

@@ -95,6 +95,13 @@ ListLayout list_layout(int P, int K, uint32_t gx, uint32_t gy);
 size_t reduce_temp_bytes(int P);
 hipError_t launch_list_binning(const FwdParams& p, const GeomState& gs, const int* radii, const BinningState& bs,
                                const TileState& ts, int K, hipStream_t stream);
+// the device-sized exclusive scan of the counting passes: in[0, n) into out[0, n], n = n_dev ? mul * *n_dev : n_host,
+// cap >= n the host's bound; `sums` holds scan_sums_count(cap) words (gsr_debug_scan_excl runs it alone)
+uint32_t scan_sums_count(size_t cap);
+hipError_t launch_scan_excl(const uint32_t* in, uint32_t* out, size_t cap, uint32_t n_host, const uint32_t* n_dev,
+                            uint32_t mul, uint32_t* sums, hipStream_t stream);
+// the file's structural constants (gsr_debug_list_constants): writes min(n, count) of them, returns count
+int list_constants(int* out, int n);
 
 
 // render_fwd.hip

@@ -899,4 +899,13 @@ hipError_t launch_list_binning(const FwdParams& p, const GeomState& gs, const in
     return hipGetLastError();
 }
 
+// the structural constants above, in the order of gsr_debug_list_constants (include/gsr.h)
+int list_constants(int* out, int n) {
+    const int c[] = {kRowSeg, kRowSegBig, kRowSegBigP, kTileSeg, kRecSpans, (int)kCoopCap, kEmitCapW,
+                     kEmitPlanes, kCoopMaxGx, kCoopBlocks, kTileBlocks, kScanTile, kScanItems, kMaxGrid};
+    constexpr int count = (int)(sizeof(c) / sizeof(c[0]));
+    for (int i = 0; i < count && i < n; i++) out[i] = c[i];
+    return count;
+}
+
 }  // namespace gsr

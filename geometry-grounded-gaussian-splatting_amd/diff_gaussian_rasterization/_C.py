@@ -113,6 +113,12 @@ def _load():
     L.gsr_debug_depth_sort_bytes.argtypes = [i]
     L.gsr_debug_depth_sort.restype = i
     L.gsr_debug_depth_sort.argtypes = [i, vp, vp, vp, vp, i, vp]
+    L.gsr_debug_list_constants.restype = i
+    L.gsr_debug_list_constants.argtypes = [ctypes.POINTER(i), i]
+    L.gsr_debug_scan_excl_bytes.restype = ctypes.c_longlong
+    L.gsr_debug_scan_excl_bytes.argtypes = [ctypes.c_longlong]
+    L.gsr_debug_scan_excl.restype = i
+    L.gsr_debug_scan_excl.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_uint, vp, ctypes.c_uint, vp, vp]
     L.gsr_timing_enable.argtypes = [i]
     L.gsr_timing_stage_mask.argtypes = [ctypes.c_uint]
     L.gsr_timing_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i)]
@@ -260,6 +266,62 @@ def debug_depth_sort(keys, prepared: bool = True):
         _check(L.gsr_debug_depth_sort(P, _ptr(keys), _ptr(keys_sorted), _ptr(order), _ptr(scratch),
                                       int(bool(prepared)), _stream(keys.device)))
     return order, keys_sorted
+
+
+LIST_CONSTANTS = ("kRowSeg", "kRowSegBig", "kRowSegBigP", "kTileSeg", "kRecSpans", "kCoopCap", "kEmitCapW",
+                  "kEmitPlanes", "kCoopMaxGx", "kCoopBlocks", "kTileBlocks", "kScanTile", "kScanItems", "kMaxGrid")
+
+
+def debug_list_constants() -> dict:
+    """The structural constants of csrc/tilelists.hip by name (gsr_debug_list_constants;
+    host only, no GPU needed)."""
+    out = (ctypes.c_int * len(LIST_CONSTANTS))()
+    n = _load().gsr_debug_list_constants(out, len(LIST_CONSTANTS))
+    if n != len(LIST_CONSTANTS):
+        raise RuntimeError(f"gsr: debug_list_constants: the library has {n} constants, these bindings name "
+                           f"{len(LIST_CONSTANTS)}")
+    return dict(zip(LIST_CONSTANTS, out))
+
+
+def debug_scan_excl_bytes(cap: int) -> int:
+    """Scratch bytes of debug_scan_excl for a bound of `cap` words (gsr_debug_scan_excl_bytes; host only)."""
+    n = _load().gsr_debug_scan_excl_bytes(int(cap))
+    if n < 0:
+        raise RuntimeError(f"gsr: debug_scan_excl_bytes({cap}): cap must be in [0, 2^31)")
+    return n
+
+
+def debug_scan_excl(inp, out, cap: int, n: int = 0, n_dev=None, mul: int = 1) -> None:
+    """The tile lists' device-sized exclusive scan alone (gsr_debug_scan_excl), in place on the caller's
+    tensors: out[0:N] = the exclusive prefix sums (mod 2^32) of inp[0:N], out[N] = their total, with
+    N = `n`, or mul * n_dev[0] read on the device when the one-word tensor `n_dev` is given.  `cap` >= N is
+    the host's bound that sizes the launch; inp holds at least cap words and is 16-byte aligned, out at
+    least cap + 1.  Nothing of inp past N is read and nothing of out past N written."""
+    bits32 = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+    for name, t, words in (("inp", inp, int(cap)), ("out", out, int(cap) + 1)) + (
+            (("n_dev", n_dev, 1),) if n_dev is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"gsr debug_scan_excl: `{name}` must be a HIP device tensor")
+        if t.dtype not in bits32 or t.dim() != 1:
+            raise RuntimeError(f"gsr debug_scan_excl: `{name}` must be a 1-D int32 / uint32 tensor (got {t.dtype}, "
+                               f"{t.dim()}-D)")
+        if not t.is_contiguous():
+            raise RuntimeError(f"gsr debug_scan_excl: `{name}` must be contiguous")
+        if t.numel() < words:
+            raise RuntimeError(f"gsr debug_scan_excl: `{name}` holds {t.numel()} words, needs {words}")
+    if inp.data_ptr() % 16:
+        raise RuntimeError("gsr debug_scan_excl: `inp` must be 16-byte aligned")
+    cap, mul = int(cap), int(mul)
+    N = int(n) if n_dev is None else mul * (int(n_dev[0].item()) & 0xFFFFFFFF)  # (a test hook: one readback)
+    if not 0 <= N <= cap or not 0 <= mul < 2 ** 32:
+        raise RuntimeError(f"gsr debug_scan_excl: length {N} outside [0, cap = {cap}]")
+    L = _load()
+    sums = torch.empty(debug_scan_excl_bytes(cap), dtype=torch.uint8, device=inp.device)
+    with torch.cuda.device(inp.device):
+        _check(L.gsr_debug_scan_excl(ctypes.c_void_p(inp.data_ptr()), ctypes.c_void_p(out.data_ptr()), cap,
+                                     0 if n_dev is not None else N,
+                                     None if n_dev is None else ctypes.c_void_p(n_dev.data_ptr()), mul, _ptr(sums),
+                                     _stream(inp.device)))
 
 
 def set_option(opt: int, value: int) -> None:

@@ -818,6 +818,25 @@ int gsr_debug_depth_sort(int P, const uint32_t* keys, uint32_t* keys_sorted, uin
                          void* scratch, int prepared, void* stream);
 
 /*
+ * The tile-list binning (csrc/tilelists.hip) for its tests (test hooks, no
+ * reference equivalent; additive to ABI 20).
+ */
+/* host only: the structural constants of tilelists.hip, in this order: kRowSeg, kRowSegBig, kRowSegBigP,
+ * kTileSeg, kRecSpans, kCoopCap, kEmitCapW, kEmitPlanes, kCoopMaxGx, kCoopBlocks, kTileBlocks, kScanTile,
+ * kScanItems, kMaxGrid.  Writes the first min(n, 14) into out and returns their number (14); -1 for n < 0 or
+ * a missing `out`. */
+int gsr_debug_list_constants(int* out, int n);
+/* bytes of `sums` for a bound of `cap` words; -1 for cap < 0 or cap >= 2^31 */
+long long gsr_debug_scan_excl_bytes(long long cap);
+/* launch_scan_excl alone: out[0, n) = the exclusive prefix sums (mod 2^32) of in[0, n) and out[n] = their total,
+ * with n = n_dev ? mul * *n_dev (read on the device) : n_host; n <= cap, the host's bound, which sizes the
+ * launch.  in: cap words, 16-byte aligned, of which only [0, n) are read; out: cap + 1 words, of which only
+ * [0, n] are written; sums: gsr_debug_scan_excl_bytes(cap) bytes of scratch.  All pointers but `stream` are
+ * device memory.  Stream-ordered, no host synchronisation. */
+int gsr_debug_scan_excl(const uint32_t* in, uint32_t* out, long long cap, uint32_t n_host, const uint32_t* n_dev,
+                        uint32_t mul, void* sums, void* stream);
+
+/*
  * Densification (csrc/densify.hip): GaussianModel.densify_and_prune
  * (scene/gaussian_model.py:797-816 with its clone / split / prune helpers),
  * compute_3D_filter (:225-262) and reset_opacity (:521-539).  Additive to

@@ -217,10 +217,15 @@ def test_library_exports_header_symbols():
     header = open(os.path.join(ROOT, "include", "gsr.h")).read()
     names = sorted(set(re.findall(r"^\s*(?:int|const char\*)\s+(gsr_\w+)\s*\(", header, re.M)))
     assert "gsr_rasterize_forward" in names and "gsr_rasterize_backward" in names and "gsr_mark_visible" in names
+    # the test hooks (additive to ABI 20)
+    assert {"gsr_debug_depth_sort", "gsr_debug_depth_sort_tile_keys", "gsr_debug_list_constants",
+            "gsr_debug_scan_excl"} <= set(names)
+    sizes = sorted(set(re.findall(r"^\s*long long\s+(gsr_\w+)\s*\(", header, re.M)))
+    assert {"gsr_debug_depth_sort_bytes", "gsr_debug_scan_excl_bytes"} <= set(sizes)
     from diff_gaussian_rasterization import _C
 
     lib = ctypes.CDLL(_C.loaded_library_path())
-    for n in names:
+    for n in names + sizes:
         assert hasattr(lib, n), n
     lib.gsr_abi_version.restype = ctypes.c_int
     assert lib.gsr_abi_version() == _C.ABI_VERSION == 20
@@ -326,3 +331,76 @@ def test_debug_depth_sort_sizes_host_only():
     assert all(a <= b for a, b in zip(nbytes, nbytes[1:])), list(zip(sizes, nbytes))
     # room for what the hook carves: tiles_touched [P], the sort's alternate keys and values [P] each
     assert all(b >= 12 * P for P, b in zip(sizes, nbytes))
+
+
+def test_debug_list_constants_host_only():
+    """The structural constants of tilelists.hip (host-only call): every name,
+    in the header's order, and the relations the kernels are built on (a
+    tile-pass segment is one round of the coop kernel's four two-plane waves,
+    segments are whole 64-entry chunks, a scan tile is 256 threads' items)."""
+    from diff_gaussian_rasterization import _C
+
+    header = open(os.path.join(ROOT, "include", "gsr.h")).read()
+    doc = header[header.index("the structural constants of tilelists.hip"):header.index("int gsr_debug_list_constants")]
+    assert tuple(re.findall(r"\bk[A-Z]\w+", doc)) == _C.LIST_CONSTANTS
+    c = _C.debug_list_constants()
+    assert tuple(c) == _C.LIST_CONSTANTS and all(isinstance(v, int) and v > 0 for v in c.values())
+    assert c["kRowSeg"] % 64 == 0 and c["kRowSegBig"] % 64 == 0 and c["kTileSeg"] % 64 == 0
+    assert c["kTileSeg"] == 2 * c["kCoopMaxGx"]  # 64 lanes x kCoopWaves x 2 planes; kCoopMaxGx = 64 kCoopWaves
+    assert c["kScanTile"] == 256 * c["kScanItems"] and c["kScanItems"] % 4 == 0
+    assert c["kCoopBlocks"] % 8 == 0 and c["kTileBlocks"] % 8 == 0
+    assert c["kCoopMaxGx"] < c["kMaxGrid"] < 2 ** 16  # spans pack lo | hi << 16
+    lib = ctypes.CDLL(_C.loaded_library_path())
+    n = len(_C.LIST_CONSTANTS)
+    assert lib.gsr_debug_list_constants(None, 0) == n
+    assert lib.gsr_debug_list_constants(None, 3) == -1 and lib.gsr_debug_list_constants(None, -1) == -1
+    few = (ctypes.c_int * 4)(-7, -7, -7, -7)
+    assert lib.gsr_debug_list_constants(few, 3) == n
+    assert list(few) == [c["kRowSeg"], c["kRowSegBig"], c["kRowSegBigP"], -7]
+
+
+def test_debug_scan_excl_refuses_cpu_and_bad_arguments(monkeypatch):
+    """debug_scan_excl takes 32-bit integer HIP tensors of the stated sizes
+    only; its scratch size is a host-only call."""
+    from diff_gaussian_rasterization import _C
+
+    # The stand-in device tensors below are host memory: no case may reach the launch (host pointers would go
+    # to a HIP kernel).  Every one is refused by the binding's own checks; the library entry is replaced for
+    # the test so that a case that got past them fails here instead.
+    def _no_launch(*args):
+        raise AssertionError("debug_scan_excl reached the library with a stand-in tensor")
+
+    monkeypatch.setattr(_C._load(), "gsr_debug_scan_excl", _no_launch)
+
+    T = _C.debug_list_constants()["kScanTile"]
+    assert [_C.debug_scan_excl_bytes(cap) for cap in (0, T - 1, T, 5 * T + 3)] == [4, 4, 8, 24]
+    for cap in (-1, 2 ** 31):
+        with pytest.raises(RuntimeError, match="cap must be in"):
+            _C.debug_scan_excl_bytes(cap)
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32)  # noqa: E731
+    with pytest.raises(RuntimeError, match="`inp` must be a HIP device tensor"):
+        _C.debug_scan_excl(i32(8), i32(9), 8, 8)
+
+    class _Dev(torch.Tensor):
+        is_cuda = True
+
+    dev = lambda t: t.as_subclass(_Dev)  # noqa: E731
+    with pytest.raises(RuntimeError, match="`out` must be a HIP device tensor"):
+        _C.debug_scan_excl(dev(i32(8)), i32(9), 8, 8)
+    with pytest.raises(RuntimeError, match="`inp` must be a 1-D int32 / uint32"):
+        _C.debug_scan_excl(dev(torch.zeros(8)), dev(i32(9)), 8, 8)
+    with pytest.raises(RuntimeError, match="`out` must be a 1-D int32 / uint32"):
+        _C.debug_scan_excl(dev(i32(8)), dev(torch.zeros(9, dtype=torch.int64)), 8, 8)
+    with pytest.raises(RuntimeError, match="`inp` must be contiguous"):
+        _C.debug_scan_excl(dev(i32(16)[::2]), dev(i32(9)), 8, 8)
+    with pytest.raises(RuntimeError, match="`inp` holds 8 words, needs 9"):
+        _C.debug_scan_excl(dev(i32(8)), dev(i32(10)), 9, 8)
+    with pytest.raises(RuntimeError, match="`out` holds 8 words, needs 9"):
+        _C.debug_scan_excl(dev(i32(8)), dev(i32(8)), 8, 8)
+    with pytest.raises(RuntimeError, match="`n_dev` must be a HIP device tensor"):
+        _C.debug_scan_excl(dev(i32(8)), dev(i32(9)), 8, 0, n_dev=i32(1), mul=1)
+    with pytest.raises(RuntimeError, match="16-byte aligned"):
+        _C.debug_scan_excl(dev(i32(12)[1:]), dev(i32(12)), 8, 8)
+    for n in (9, -1):
+        with pytest.raises(RuntimeError, match="outside"):
+            _C.debug_scan_excl(dev(i32(8)), dev(i32(9)), 8, n)

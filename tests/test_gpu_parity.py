@@ -54,50 +54,13 @@ def _fwd_args(c, colors_precomp=None, cov3D=None, scale_modifier=1.0):
     return a
 
 
-def _check_binning(out, o, H, W, dead_sample=None):
-    """Per-tile Gaussian lists against the oracle's (the reference's stable
-    (tile, depth) sort order): ours is the oracle's list with the instances
-    the tile test culls removed, in the same order, and every removed
-    instance is dead — power > 0 or alpha < 1/255 at every pixel of its tile
-    (checked for all of them, or for `dead_sample` random ones)."""
-    from diff_gaussian_rasterization import _C
-
-    plist, ranges = _C.debug_binning(out[7], out[9], out[0], H, W)
-    ob = o["state"].binning()["point_list"].astype(np.int64)
-    oranges = o["state"].tile_state()["ranges"].astype(np.int64)
-    tiles = ranges.shape[0]
-
-    def keys(pl, rg):
-        tile = np.repeat(np.arange(tiles, dtype=np.int64), rg[:, 1] - rg[:, 0])
-        ent = np.concatenate([pl[a:b] for a, b in rg]) if len(pl) else np.zeros(0, np.int64)
-        return (tile << 32) | ent.astype(np.int64)
-
-    ours = keys(plist.astype(np.int64), ranges.astype(np.int64))
-    ref = keys(ob, oranges)
-    assert len(ours) <= len(ref) == out[0]
-    srt = np.argsort(ref, kind="stable")
-    at = np.searchsorted(ref[srt], ours)
-    assert np.all(at < len(ref)) and np.array_equal(ref[srt][np.minimum(at, len(ref) - 1)], ours)
-    pos = srt[at]
-    assert np.all(np.diff(pos) > 0)  # same relative order in every tile
-    dropped = ref[~np.isin(ref, ours)]
-    if dead_sample is not None and len(dropped) > dead_sample:
-        dropped = np.random.default_rng(0).choice(dropped, dead_sample, replace=False)
-    geo = o["state"].geometry()
-    gx = (W + 15) // 16
-    py, px = np.mgrid[0:16, 0:16]
-    for k in dropped:
-        t, g = int(k >> 32), int(k & 0xFFFFFFFF)
-        ty, tx = divmod(t, gx)
-        x = (tx * 16 + px).ravel().astype(np.float64)
-        y = (ty * 16 + py).ravel().astype(np.float64)
-        keep = (x < W) & (y < H)
-        mx, my = geo["means2D"][g].astype(np.float64)
-        a, b, c, op = geo["conic_opacity"][g].astype(np.float64)
-        dx, dy = mx - x[keep], my - y[keep]
-        power = -0.5 * (a * dx * dx + c * dy * dy) - b * dx * dy
-        alpha = np.minimum(0.99, op * np.exp(np.minimum(power, 0.0)))
-        assert np.all((power > 0) | (alpha < 1.0 / 255.0)), (t, g)
+# the binning rule and the scene-shaping helpers live in helpers.py (tests/test_gpu_tilelists.py shares them)
+_check_binning = Hh.check_binning
+_with_depth_ties = Hh.with_depth_ties
+_place = Hh.place
+_reshape = Hh.reshape
+_surely_live_tiles = Hh.surely_live_tiles
+_gpu_entries_of = Hh.gpu_entries_of
 
 
 def _run(c, colors_precomp=None, cov3D=None, scale_modifier=1.0, check_bwd=True, gpu_views=None):
@@ -400,16 +363,6 @@ def test_cov3d_precomp_path_pinned_to_reference_covariance(geom):
         assert l2 <= 2 * o_l2 + 1e-5 and l2 <= 3e-4, (name, l2, o_l2)
 
 
-def _with_depth_ties(c, n_tied):
-    """Gaussians n_tied..2 n_tied-1 get the means of 0..n_tied-1: bit-identical
-    depths, so the per-tile order of each pair is decided by the index alone
-    (the reference's stable sort, rasterizer_impl.cu:403-412)."""
-    m = c["inp"]["means3D"].clone()
-    m[n_tied:2 * n_tied] = m[:n_tied]
-    c["inp"]["means3D"] = m.contiguous()
-    return c
-
-
 def test_parity_depth_ties():
     _run(_with_depth_ties(Hh.small_case(P=600, W=64, H=48, seed=21), 250))
 
@@ -431,54 +384,6 @@ def test_parity_depth_sort_tiles(P):
 def test_parity_binning_paths():
     _run(Hh.small_case(P=10000, W=256, H=256, seed=7, log_scale=math.log(0.03)))
     _run(Hh.small_case(P=500, W=100, H=70, seed=2, kernel_size=0.1))
-
-
-def _place(c, idx, px, py, z):
-    """Gaussians `idx` moved to pixel centres (px, py) at depth z (identity camera:
-    pixel = ((ndc + 1) size - 1) / 2)."""
-    f32 = lambda v: torch.as_tensor(np.asarray(v), dtype=torch.float32)  # noqa: E731
-    px, py, z = f32(px), f32(py), f32(z)
-    m = c["inp"]["means3D"].clone()
-    m[idx, 0] = ((2 * px + 1) / c["W"] - 1) * z * c["tanx"]
-    m[idx, 1] = ((2 * py + 1) / c["H"] - 1) * z * c["tany"]
-    m[idx, 2] = z
-    c["inp"]["means3D"] = m.contiguous()
-
-
-def _reshape(c, idx, scale, opacity=0.8):
-    """Gaussians `idx` axis-aligned with scales `scale` (x, y, z) and the given opacity."""
-    s, r, op = (c["inp"][k].clone() for k in ("scales", "rotations", "opacities"))
-    s[idx] = torch.tensor(scale, dtype=torch.float32)
-    r[idx] = torch.tensor([1.0, 0.0, 0.0, 0.0])
-    op[idx] = opacity
-    c["inp"].update(scales=s.contiguous(), rotations=r.contiguous(), opacities=op.contiguous())
-
-
-def _surely_live_tiles(o, g, W, H):
-    """Tiles that Gaussian g certainly keeps after tile culling, from the
-    oracle's geometry: those holding a pixel of the row or the column through
-    its centre with power <= 0 and alpha >= 2/255 (twice the cull's 1/255, so no
-    rounding decides it).  A lower bound of its live tiles; set of (ty, tx)."""
-    geo = o["state"].geometry()
-    mx, my = geo["means2D"][g].astype(np.float64)
-    a, b, cc, op = geo["conic_opacity"][g].astype(np.float64)
-    x0, y0 = int(np.clip(round(mx), 0, W - 1)), int(np.clip(round(my), 0, H - 1))
-    live = set()
-    for xs, ys in ((np.arange(W, dtype=np.float64), np.full(W, float(y0))),
-                   (np.full(H, float(x0)), np.arange(H, dtype=np.float64))):
-        dx, dy = mx - xs, my - ys
-        power = -0.5 * (a * dx * dx + cc * dy * dy) - b * dx * dy
-        ok = (power <= 0) & (op * np.exp(np.minimum(power, 0.0)) >= 2.0 / 255.0)
-        live |= set(zip((ys[ok] // 16).astype(int).tolist(), (xs[ok] // 16).astype(int).tolist()))
-    return live
-
-
-def _gpu_entries_of(out, g, H, W):
-    """How many per-tile list entries of the GPU forward name Gaussian g."""
-    from diff_gaussian_rasterization import _C
-
-    plist, ranges = _C.debug_binning(out[7], out[9], out[0], H, W)
-    return int((plist[:int(ranges[:, 1].max())] == g).sum())
 
 
 def test_parity_binning_coop_emission_16bit():

@@ -112,6 +112,18 @@ def test_query_wide_grid_sort_path():
     _check(c, sample_points(c, 5000, 11))
 
 
+def test_query_narrowest_wide_list_grid():
+    """kCoopMaxGx + 1 tiles across: the Gaussian lists of the point queries (cull pad 0.5) come from
+    tilelists.hip's tiles_emit_wide_kernel and list_ranges_kernel."""
+    from diff_gaussian_rasterization import _C
+
+    k = _C.debug_list_constants()
+    gx = k["kCoopMaxGx"] + 1
+    assert gx <= k["kMaxGrid"]
+    c = Hh.small_case(P=600, W=16 * gx, H=40, seed=15, log_scale=math.log(0.01))
+    _check(c, sample_points(c, 5000, 16))
+
+
 def test_query_degenerate():
     from diff_gaussian_rasterization import _C
 
