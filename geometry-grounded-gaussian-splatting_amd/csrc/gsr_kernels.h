@@ -448,6 +448,79 @@ hipError_t launch_nearest_qsort(long long Q, const double* query, const PointGri
 hipError_t launch_nearest_search(long long Q, const double* query, long long R, const PointGrid& g,
                                  const PointNearestState& s, double max_dist, double* out, hipStream_t stream);
 
+// TnT F-score evaluation (tnteval.hip): polygon-volume crop, voxel-mean grid, a nearest-point index built
+// once and queried many times, the ICP correspondence sums, an in-place 4x4; float64
+constexpr int kCropMaxVertices = 1024;  // GSR_CROP_MAX_VERTICES: the polygon's (u, v) pairs fill 16 KB of LDS
+constexpr int kIcpMaxSums = 10;         // sums of one accumulate pass (8 or 10), then the bad-index count
+struct CropParams {    // by value into the kernels
+    double T[12];      // rows 0-2 of the 4x4
+    int has_T;
+    int u, v, w;       // axes of the polygon plane and of the extrusion
+    double axis_min, axis_max;
+    int M;             // polygon vertices
+};
+struct CropState {
+    double* poly;     // [M,3] the polygon on the device
+    uint32_t* flags;  // [N + 1] kept, then their exclusive scan: flags[N] = the number kept
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct VoxelGrid {     // by value into the kernels
+    double origin[3];  // min_bound - 0.5 voxel
+    double voxel;
+    int by, bz;        // key = cx << (by + bz) | cy << bz | cz
+};
+struct VoxelState {
+    double* partials;
+    double* bounds;         // [6] min xyz, max xyz
+    uint64_t* keys;         // [N] in input order
+    uint64_t* keys_sorted;  // [N]
+    uint32_t* order;        // [N] input position of each sorted point (a cell's points ascending)
+    uint32_t* flags;        // [N + 1] (over keys) run heads, then their exclusive scan: flags[N] = cells
+    uint32_t* bad;          // a coordinate is not finite
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct PointIndexView {  // the caller's index buffer, carved
+    uint64_t* keys;      // [R] sorted packed cell keys
+    uint32_t* order;     // [R] original position of each sorted point
+    double *x, *y, *z;   // [R] ref in key order
+};
+struct PointIndexBuildState {
+    double* partials;
+    double* bounds;
+    uint64_t* keys;  // [R] unsorted
+    void* tmp;
+    size_t tmp_bytes;
+};
+struct IcpState {
+    double* partials;  // [kPeReduceBlocks][kIcpMaxSums + 1]
+    double* sums;      // [kIcpMaxSums + 1]
+};
+size_t carve_crop(void* base, long long N, int M, CropState& s);
+size_t carve_voxel(void* base, long long N, VoxelState& s);
+size_t carve_point_index(void* base, long long R, PointIndexView& v);
+size_t carve_point_index_build(void* base, long long R, PointIndexBuildState& s);
+size_t carve_point_query(void* base, long long Q, PointNearestState& s);
+size_t carve_icp(void* base, IcpState& s);
+hipError_t launch_crop_plan(long long N, const double* points, const CropParams& p, const CropState& s,
+                            hipStream_t stream);
+hipError_t launch_crop_write(long long N, const double* points, const CropParams& p, const CropState& s,
+                             long long* kept, double* out, hipStream_t stream);
+hipError_t launch_voxel_keys(long long N, const double* points, const VoxelGrid& g, const VoxelState& s,
+                             hipStream_t stream);
+hipError_t launch_voxel_sort(long long N, unsigned bits, const VoxelState& s, hipStream_t stream);
+hipError_t launch_voxel_plan(long long N, const VoxelState& s, hipStream_t stream);
+hipError_t launch_voxel_emit(long long N, const double* points, const VoxelGrid& g, const VoxelState& s, double* means,
+                             long long* counts, long long* cells, hipStream_t stream);
+hipError_t launch_index_search(long long Q, const double* query, long long R, const PointGrid& g,
+                               const PointIndexView& v, const PointNearestState& s, double max_dist, double* dist,
+                               long long* index, hipStream_t stream);
+hipError_t launch_index_fill(long long Q, double* dist, long long* index, hipStream_t stream);
+hipError_t launch_icp_accumulate(int pass, long long N, const double* src, long long R, const double* ref,
+                                 const long long* index, const double* means6, const IcpState& s, hipStream_t stream);
+hipError_t launch_points_transform(long long N, double* points, const double* T12, hipStream_t stream);
+
 // densify.hip: densify / prune plan and gather, radix-select quantile, 3D filter, opacity reset
 constexpr int kMaxDensifyParams = 16;
 enum : int { kDensifyCopy = 0, kDensifyXyz = 1, kDensifyScaling = 2 };

@@ -1,0 +1,494 @@
+"""Tanks and Temples F-score evaluation on the device (the reference's
+eval_tnt/run.py, which is open3d on the CPU) over the C ABI: polygon-volume
+crop, voxel-mean grid, a nearest-point index built once and queried many
+times, and the correspondence sums of point-to-point ICP in HIP
+(gsr_points_crop_polygon, gsr_points_voxel_mean, gsr_points_index_build /
+_query, gsr_icp_accumulate, gsr_points_transform; csrc/tnteval.hip); the 3x3
+SVD of each ICP update, the readers and the camera-centre RANSAC on the host in
+numpy float64.  All geometry is float64.
+
+    crop = read_crop_volume("Barn.json")
+    init = trajectory_alignment(est_centers, gt_centers, gt_trans, np.random.default_rng(0))
+    out = tnt_fscore(vertices, faces, gt_points, crop, init, SCENES_TAU["Barn"])
+    out["precision"], out["recall"], out["fscore"]
+
+Device tensors on the current stream; there is no CPU path.  Every device call
+returns a stats dict as its last value: scratch_bytes, and stage_ms (GPU
+milliseconds per stage) when `measure_stages` is set — measuring synchronises,
+so it is off by default and stage_ms is then None.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import math
+
+import numpy as np
+import torch
+
+from diff_gaussian_rasterization import _C as _G
+from gsr_eval import _require_points
+from gsr_mesh import _Out, _require
+
+SCENES_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003,
+              "Meetingroom": 0.01, "Truck": 0.005}
+MAX_POINT_NUMBER = 4e6
+CROP_MAX_VERTICES = 1024  # GSR_CROP_MAX_VERTICES
+CROP_STAGES = ("flags_scan", "write")
+VOXEL_STAGES = ("bounds", "keys", "sort", "heads_scan", "emit")
+BUILD_STAGES = ("bounds", "ref_sort")
+QUERY_STAGES = ("query_sort", "search")
+ICP_STAGES = ("sums",)
+TRANSFORM_STAGES = ("transform",)
+_AXIS = {"X": 0, "Y": 1, "Z": 2}
+measure_stages = False
+
+
+class _PointIndex(ctypes.Structure):  # gsr_point_index
+    _fields_ = [("R", ctypes.c_longlong), ("buffer", ctypes.c_void_p), ("bounds_min", ctypes.c_double * 3),
+                ("bounds_max", ctypes.c_double * 3), ("cell_size", ctypes.c_double), ("cells", ctypes.c_longlong * 3),
+                ("key_bits", ctypes.c_int * 3)]
+
+
+def _lib():
+    L = _G._load()
+    if not getattr(L, "_tnteval_bound", False):
+        vp, i, ll, d, A = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _G._ALLOC
+        fp, dp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
+        L.gsr_points_crop_polygon.restype = i
+        L.gsr_points_crop_polygon.argtypes = [A, vp, A, vp, A, vp, ll, vp, dp, i, d, d, i, dp, ctypes.POINTER(ll), fp,
+                                              vp]
+        L.gsr_points_voxel_mean.restype = i
+        L.gsr_points_voxel_mean.argtypes = [A, vp, A, vp, A, vp, A, vp, ll, vp, d, ctypes.POINTER(ll), fp, vp]
+        L.gsr_points_index_bytes.restype = ctypes.c_size_t
+        L.gsr_points_index_bytes.argtypes = [ll]
+        L.gsr_points_index_build.restype = i
+        L.gsr_points_index_build.argtypes = [A, vp, ll, vp, vp, ctypes.c_size_t, ctypes.POINTER(_PointIndex), fp, vp]
+        L.gsr_points_index_query.restype = i
+        L.gsr_points_index_query.argtypes = [A, vp, ctypes.POINTER(_PointIndex), ll, vp, d, vp, vp, fp, vp]
+        L.gsr_icp_accumulate.restype = i
+        L.gsr_icp_accumulate.argtypes = [A, vp, ll, vp, ll, vp, vp, i, dp, dp, fp, vp]
+        L.gsr_points_transform.restype = i
+        L.gsr_points_transform.argtypes = [ll, vp, dp, fp, vp]
+        L._tnteval_bound = True
+    return L
+
+
+def _ms():
+    return (ctypes.c_float * 8)() if measure_stages else None
+
+
+def _stats(stages, ms, scratch=None, **extra):
+    return dict(stage_ms=None if ms is None else {k: float(ms[i]) for i, k in enumerate(stages)},
+                scratch_bytes=sum(int(b.numel()) for b in scratch.blocks) if scratch is not None else 0, **extra)
+
+
+def _check(L, rc):
+    if rc != 0:
+        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+
+
+def _mat4(T, who):
+    T = np.ascontiguousarray(np.asarray(T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T,
+                                        dtype=np.float64))
+    if T.shape != (4, 4):
+        raise RuntimeError(f"{who}: a transform must have shape (4, 4) (got {T.shape})")
+    return T
+
+
+def _dptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+# ---- readers -----------------------------------------------------------------------------------------------------
+
+def read_crop_volume(path):
+    """The crop file of a TnT scene (open3d's SelectionPolygonVolume JSON) -> dict: orthogonal_axis "X" / "Y" /
+    "Z", axis_min, axis_max, bounding_polygon [M,3] float64."""
+    with open(path) as fh:
+        data = json.load(fh)
+    axis = str(data["orthogonal_axis"]).upper()
+    if axis not in _AXIS:
+        raise RuntimeError(f"read_crop_volume: orthogonal_axis must be X, Y or Z (got {data['orthogonal_axis']!r})")
+    poly = np.asarray(data["bounding_polygon"], dtype=np.float64).reshape(-1, 3)
+    return {"orthogonal_axis": axis, "axis_min": float(data["axis_min"]), "axis_max": float(data["axis_max"]),
+            "bounding_polygon": poly}
+
+
+def read_trajectory(path):
+    """The .log trajectory format: per camera a metadata line of integers, then the four rows of its 4x4 pose
+    -> (metadata [n] lists of int, poses [n,4,4] float64)."""
+    meta, poses = [], []
+    with open(path) as fh:
+        lines = [ln for ln in fh.read().split("\n")]
+    k = 0
+    while k < len(lines) and lines[k].strip():
+        meta.append([int(x) for x in lines[k].split()])
+        rows = [np.array(lines[k + 1 + r].split(), dtype=np.float64) for r in range(4)]
+        if any(r.shape != (4,) for r in rows):
+            raise RuntimeError(f"read_trajectory: {path}: a pose row without four numbers after line {k + 1}")
+        poses.append(np.stack(rows))
+        k += 5
+    return meta, np.array(poses, dtype=np.float64).reshape(-1, 4, 4)
+
+
+# ---- device calls ------------------------------------------------------------------------------------------------
+
+@torch.no_grad()
+def crop_points(points, crop, transform=None):
+    """open3d's SelectionPolygonVolume.crop_point_cloud after an optional 4x4: points [N,3] float64 ->
+    (kept_index [K] int64 ascending, kept transformed points [K,3] float64, stats)."""
+    who = "crop_points"
+    _require_points(points, "points", who)
+    dev = points.device
+    points = points.contiguous()
+    poly = np.ascontiguousarray(np.asarray(crop["bounding_polygon"], dtype=np.float64).reshape(-1, 3))
+    T = None if transform is None else _mat4(transform, who)
+    L = _lib()
+    kept, out, scratch = _Out(dev, torch.int64), _Out(dev, torch.float64), _G._ScratchBlocks(dev)
+    K, ms = ctypes.c_longlong(0), _ms()
+    with torch.cuda.device(dev):
+        rc = L.gsr_points_crop_polygon(kept.cb, None, out.cb, None, scratch.cb, None, points.size(0), _G._ptr(points),
+                                       None if T is None else _dptr(T), _AXIS[crop["orthogonal_axis"]],
+                                       float(crop["axis_min"]), float(crop["axis_max"]), poly.shape[0], _dptr(poly),
+                                       ctypes.byref(K), ms, _G._stream(dev))
+    _check(L, rc)
+    return kept.tensor[:K.value], out.tensor[:3 * K.value].view(-1, 3), _stats(CROP_STAGES, ms, scratch)
+
+
+@torch.no_grad()
+def voxel_down_sample(points, voxel_size, return_cells=False):
+    """open3d's PointCloud.voxel_down_sample: points [N,3] float64 -> (means [C,3] float64, one per occupied
+    voxel, ascending in the voxel's (cx, cy, cz); stats) or, with return_cells, (means, counts [C] int64, cells
+    [C,3] int64, stats)."""
+    who = "voxel_down_sample"
+    _require_points(points, "points", who)
+    dev = points.device
+    points = points.contiguous()
+    L = _lib()
+    means, counts, cells = _Out(dev, torch.float64), _Out(dev, torch.int64), _Out(dev, torch.int64)
+    scratch = _G._ScratchBlocks(dev)
+    C, ms = ctypes.c_longlong(0), _ms()
+    with torch.cuda.device(dev):
+        rc = L.gsr_points_voxel_mean(means.cb, None, counts.cb, None, cells.cb, None, scratch.cb, None, points.size(0),
+                                     _G._ptr(points), float(voxel_size), ctypes.byref(C), ms, _G._stream(dev))
+    _check(L, rc)
+    st = _stats(VOXEL_STAGES, ms, scratch)
+    m = means.tensor[:3 * C.value].view(-1, 3)
+    if return_cells:
+        return m, counts.tensor[:C.value], cells.tensor[:3 * C.value].view(-1, 3), st
+    return m, st
+
+
+def uniform_down_sample(points, every_k):
+    """open3d's uniform_down_sample: every k-th point from the first."""
+    if int(every_k) < 1:
+        raise RuntimeError("uniform_down_sample: every_k must be at least 1")
+    return points[::int(every_k)]
+
+
+class NearestIndex:
+    """gsr_points_nearest's ref half, done once: NearestIndex.build(ref) -> index; index.query(query, max_dist)
+    any number of times.  The index owns its device buffer and keeps `ref` (the ICP sums read it)."""
+
+    def __init__(self, ref, buffer, desc, stats):
+        self.ref, self.buffer, self.desc, self.build_stats = ref, buffer, desc, stats
+
+    @classmethod
+    @torch.no_grad()
+    def build(cls, ref):
+        who = "NearestIndex.build"
+        _require_points(ref, "ref", who)
+        dev = ref.device
+        ref = ref.contiguous()
+        L = _lib()
+        R = ref.size(0)
+        buffer = torch.empty(int(L.gsr_points_index_bytes(R)), dtype=torch.uint8, device=dev)
+        desc, scratch, ms = _PointIndex(), _G._ScratchBlocks(dev), _ms()
+        with torch.cuda.device(dev):
+            rc = L.gsr_points_index_build(scratch.cb, None, R, _G._ptr(ref), _G._ptr(buffer), buffer.numel(),
+                                          ctypes.byref(desc), ms, _G._stream(dev))
+        _check(L, rc)
+        return cls(ref, buffer, desc, _stats(BUILD_STAGES, ms, scratch, index_bytes=int(buffer.numel())))
+
+    @torch.no_grad()
+    def query(self, query, max_dist):
+        """query [Q,3] float64 -> (dist [Q] float64, index [Q] int64, stats): the distance to and the position
+        in `ref` of the nearest point with distance < max_dist (the lowest position among equally near ones),
+        (+inf, -1) beyond."""
+        who = "NearestIndex.query"
+        _require_points(query, "query", who)
+        dev = query.device
+        if dev != self.ref.device:
+            raise RuntimeError(f"{who}: `query` must be on the device of the index")
+        query = query.contiguous()
+        Q = query.size(0)
+        dist = torch.empty(Q, dtype=torch.float64, device=dev)
+        index = torch.empty(Q, dtype=torch.int64, device=dev)
+        L = _lib()
+        scratch, ms = _G._ScratchBlocks(dev), _ms()
+        with torch.cuda.device(dev):
+            rc = L.gsr_points_index_query(scratch.cb, None, ctypes.byref(self.desc), Q, _G._ptr(query),
+                                          float(max_dist), _G._ptr(dist), _G._ptr(index), ms, _G._stream(dev))
+        _check(L, rc)
+        return dist, index, _stats(QUERY_STAGES, ms, scratch)
+
+
+@torch.no_grad()
+def icp_accumulate(source, ref, index, means=None):
+    """The sums of one ICP pass over the pairs (source[i], ref[index[i]]) with index[i] >= 0: without `means`
+    pass 1 -> [8] float64 numpy (n, sum d^2, sum s, sum t); with means [6] (m_s, m_t) pass 2 -> [10]
+    (sum (s - m_s)(t - m_t)^T row-major, sum |s - m_s|^2).  -> (sums, stats)."""
+    who = "icp_accumulate"
+    _require_points(source, "source", who)
+    _require_points(ref, "ref", who)
+    _require(index, "index", (torch.int64,), 1, who)
+    if index.size(0) != source.size(0) or ref.device != source.device or index.device != source.device:
+        raise RuntimeError(f"{who}: `index` must have one entry per source point, all on one device")
+    dev = source.device
+    source, ref, index = source.contiguous(), ref.contiguous(), index.contiguous()
+    sums = np.zeros(8 if means is None else 10, dtype=np.float64)
+    m = None if means is None else np.ascontiguousarray(np.asarray(means, dtype=np.float64).reshape(6))
+    L = _lib()
+    scratch, ms = _G._ScratchBlocks(dev), _ms()
+    with torch.cuda.device(dev):
+        rc = L.gsr_icp_accumulate(scratch.cb, None, source.size(0), _G._ptr(source), ref.size(0), _G._ptr(ref),
+                                  _G._ptr(index), 1 if m is None else 2, None if m is None else _dptr(m), _dptr(sums),
+                                  ms, _G._stream(dev))
+    _check(L, rc)
+    return sums, _stats(ICP_STAGES, ms, scratch)
+
+
+@torch.no_grad()
+def transform_points_(points, transform):
+    """points [N,3] float64 <- the 4x4, in place: p' = ((r0 x + r1 y) + r2 z) + t.  -> stats."""
+    who = "transform_points_"
+    _require_points(points, "points", who)
+    if not points.is_contiguous():
+        raise RuntimeError(f"{who}: `points` must be contiguous (it is changed in place)")
+    T = _mat4(transform, who)
+    L = _lib()
+    ms = _ms()
+    with torch.cuda.device(points.device):
+        rc = L.gsr_points_transform(points.size(0), _G._ptr(points), _dptr(T), ms, _G._stream(points.device))
+    _check(L, rc)
+    return _stats(TRANSFORM_STAGES, ms)
+
+
+# ---- ICP ---------------------------------------------------------------------------------------------------------
+
+def umeyama_from_sums(n, sum_s, sum_t, H, var_sum):
+    """Eigen's umeyama with scaling from gsr_icp_accumulate's sums (H = sum (s - m_s)(t - m_t)^T, var_sum =
+    sum |s - m_s|^2): sigma = H^T / n, SVD, S = diag(1, 1, sign(det U det V)), R = U S V^T,
+    c = tr(D S) / (var_sum / n), t = m_t - c R m_s.  -> 4x4 float64."""
+    ms, mt = np.asarray(sum_s, np.float64) / n, np.asarray(sum_t, np.float64) / n
+    U, D, Vt = np.linalg.svd(np.asarray(H, np.float64).reshape(3, 3).T / n)
+    S = np.array([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) > 0 else -1.0])
+    R = U @ np.diag(S) @ Vt
+    c = (D * S).sum() / (var_sum / n)
+    T = np.eye(4)
+    T[:3, :3] = c * R
+    T[:3, 3] = mt - c * (R @ ms)
+    return T
+
+
+@torch.no_grad()
+def registration_icp(source, target_index, max_dist, max_iter, relative_fitness=1e-6, relative_rmse=1e-6):
+    """open3d's registration_icp with TransformationEstimationPointToPoint(with_scaling=True) from the identity:
+    evaluate; up to max_iter times: the update from the current correspondences, T = update T, move the
+    source, evaluate again, stop when |d fitness| and |d rmse| are both under their bars.  fitness = n / N,
+    rmse = sqrt(sum d^2 / n) (0 when n = 0).  Without a correspondence the loop stops and the current T is
+    returned with fitness 0 (open3d leaves this undefined).  source [N,3] float64 is not changed.
+    -> dict: T [4,4] numpy, fitness, rmse, iterations, history [(fitness, rmse)], indices (the
+    correspondence index tensor of every evaluation), stats."""
+    who = "registration_icp"
+    _require_points(source, "source", who)
+    if not isinstance(target_index, NearestIndex):
+        raise RuntimeError(f"{who}: `target_index` must be a NearestIndex")
+    src = source.contiguous().clone()
+    ref = target_index.ref
+    N = src.size(0)
+    T = np.eye(4)
+    ms_iter = []
+
+    def evaluate():
+        _, idx, st_q = target_index.query(src, max_dist)
+        s1, st_a = icp_accumulate(src, ref, idx)
+        n = int(round(s1[0]))
+        ms_iter.append((st_q, st_a))
+        return idx, s1, (n / N if N else 0.0), (math.sqrt(s1[1] / n) if n else 0.0)
+
+    idx, s1, fit, rmse = evaluate()
+    history, indices, it = [(fit, rmse)], [idx], 0
+    while it < max_iter and s1[0] > 0:
+        n = s1[0]
+        s2, _ = icp_accumulate(src, ref, idx, np.concatenate([s1[2:5] / n, s1[5:8] / n]))
+        update = umeyama_from_sums(n, s1[2:5], s1[5:8], s2[:9], s2[9])
+        T = update @ T
+        transform_points_(src, update)
+        it += 1
+        prev = (fit, rmse)
+        idx, s1, fit, rmse = evaluate()
+        history.append((fit, rmse))
+        indices.append(idx)
+        if abs(prev[0] - fit) < relative_fitness and abs(prev[1] - rmse) < relative_rmse:
+            break
+    return {"T": T, "fitness": fit, "rmse": rmse, "iterations": it, "history": history, "indices": indices,
+            "stats": {"evaluations": ms_iter}}
+
+
+@torch.no_grad()
+def crop_and_downsample(points, crop, down_sample_method="voxel", voxel_size=0.01, transform=None):
+    """registration.py:113-131: transform, crop, then the voxel grid, or every k-th point once more than
+    MAX_POINT_NUMBER are left."""
+    _, p, _ = crop_points(points, crop, transform)
+    if down_sample_method == "voxel":
+        return voxel_down_sample(p, voxel_size)[0]
+    if down_sample_method == "uniform" and p.size(0) > MAX_POINT_NUMBER:
+        return uniform_down_sample(p, int(round(p.size(0) / float(MAX_POINT_NUMBER)))).contiguous()
+    return p
+
+
+def _registration(source, gt_target, init_T, crop, method, voxel_size, threshold, max_iter):
+    init = _mat4(init_T, "registration")
+    s = crop_and_downsample(source, crop, method, voxel_size, init)
+    t = crop_and_downsample(gt_target, crop, method, voxel_size)
+    index = NearestIndex.build(t)  # once per registration, not per iteration
+    reg = registration_icp(s, index, threshold, max_iter)
+    reg["T"] = reg["T"] @ init
+    reg["n_source"], reg["n_target"] = int(s.size(0)), int(t.size(0))
+    reg["stats"]["index_build"] = index.build_stats
+    return reg
+
+
+def registration_vol_ds(source, gt_target, init_T, crop, voxel_size, threshold, max_iter):
+    """registration.py:166-202: both clouds cropped and voxel-averaged at voxel_size, then ICP at `threshold`."""
+    return _registration(source, gt_target, init_T, crop, "voxel", voxel_size, threshold, max_iter)
+
+
+def registration_unif(source, gt_target, init_T, crop, threshold, max_iter):
+    """registration.py:134-163: both clouds cropped and thinned uniformly to about MAX_POINT_NUMBER."""
+    return _registration(source, gt_target, init_T, crop, "uniform", 0.01, threshold, max_iter)
+
+
+# ---- histogram and F-score ---------------------------------------------------------------------------------------
+
+def f1_score_histo(tau, plot_stretch, d1, d2):
+    """get_f1_score_histo2 (evaluation.py:173-215) over device distances d1 (precision side) and d2 (recall
+    side): the counts by torch, the bin edges by numpy's own arange, the last bin closed on the right as
+    np.histogram's.  -> dict precision, recall, fscore, n_precise, n_recalled, edges_*, cum_*."""
+    if d1.numel() == 0 or d2.numel() == 0:
+        z = np.array([0])
+        return {"precision": 0, "recall": 0, "fscore": 0, "n_precise": 0, "n_recalled": 0, "edges_source": z,
+                "cum_source": z, "edges_target": z, "cum_target": z}
+    edges_np = np.arange(0, tau * plot_stretch, tau / 100)
+    edges = torch.as_tensor(edges_np, device=d1.device)
+    nb = edges_np.shape[0] - 1
+
+    def side(d):
+        k = torch.searchsorted(edges, d.contiguous(), right=True) - 1
+        k = torch.where(d == edges[-1], torch.full_like(k, nb - 1), k)
+        ok = (k >= 0) & (k < nb)
+        hist = torch.bincount(k[ok], minlength=nb)
+        return int((d < tau).sum()), hist.cpu().numpy()
+
+    (n1, h1), (n2, h2) = side(d1), side(d2)
+    recall, precision = float(n2) / float(d2.numel()), float(n1) / float(d1.numel())
+    with np.errstate(all="ignore"):
+        fscore = float(np.float64(2 * recall * precision) / np.float64(recall + precision))
+    return {"precision": precision, "recall": recall, "fscore": fscore, "n_precise": n1, "n_recalled": n2,
+            "edges_source": edges_np, "cum_source": np.cumsum(h1).astype(float) / d1.numel(),
+            "edges_target": edges_np, "cum_target": np.cumsum(h2).astype(float) / d2.numel()}
+
+
+@torch.no_grad()
+def evaluate_histo(source, target, T, crop, voxel, tau, plot_stretch=5):
+    """EvaluateHisto (evaluation.py:60-170) without the normals and the coloured .ply files: the source moved
+    by T, both clouds cropped and voxel-averaged at `voxel`, the nearest distance each way (every point gets
+    one: the bound covers the joint box), then f1_score_histo.  -> its dict, plus n_source, n_target,
+    dist_source, dist_target, stats."""
+    s = crop_and_downsample(source, crop, "voxel", voxel, _mat4(T, "evaluate_histo"))
+    t = crop_and_downsample(target, crop, "voxel", voxel)
+    stats = {}
+    if s.size(0) and t.size(0):
+        both = torch.cat([s, t])
+        bound = 2.0 * float((both.amax(0) - both.amin(0)).norm()) + 1.0
+        ti, si = NearestIndex.build(t), NearestIndex.build(s)
+        d1, _, stats["query_source"] = ti.query(s, bound)
+        d2, _, stats["query_target"] = si.query(t, bound)
+        stats["build_target"], stats["build_source"] = ti.build_stats, si.build_stats
+    else:
+        d1 = d2 = torch.empty(0, dtype=torch.float64, device=source.device)
+    out = f1_score_histo(tau, plot_stretch, d1, d2)
+    out.update(n_source=int(s.size(0)), n_target=int(t.size(0)), dist_source=d1, dist_target=d2, stats=stats)
+    return out
+
+
+@torch.no_grad()
+def tnt_fscore(vertices, faces, gt_points, crop, init_T, tau):
+    """run.py:93-187: the evaluated cloud is the mesh's vertices followed by its face centroids ((a + b) + c) /
+    3; three registrations refine init_T (voxel tau at threshold 80 tau, voxel tau / 2 at 20 tau, uniform at
+    2 tau, 20 iterations each); then evaluate_histo at voxel tau / 2, threshold tau.  vertices [V,3] float32 /
+    float64, faces [F,3] int32 / int64, gt_points [G,3] float32 / float64.  -> dict: dTau, precision, recall,
+    fscore (what metrics.json holds), the curves, counts, transformation, registrations, stats."""
+    who = "tnt_fscore"
+    _require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
+    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
+    _require(gt_points, "gt_points", (torch.float32, torch.float64), 2, who)
+    if vertices.size(1) != 3 or faces.size(1) != 3 or gt_points.size(1) != 3:
+        raise RuntimeError(f"{who}: `vertices`, `faces` and `gt_points` must have shapes (V, 3), (F, 3), (G, 3)")
+    v, f = vertices.to(torch.float64), faces.long()
+    pcd = torch.cat([v, ((v[f[:, 0]] + v[f[:, 1]]) + v[f[:, 2]]) / 3.0]).contiguous()
+    gt = gt_points.to(torch.float64).contiguous()
+    r2 = registration_vol_ds(pcd, gt, init_T, crop, tau, tau * 80, 20)
+    r3 = registration_vol_ds(pcd, gt, r2["T"], crop, tau / 2.0, tau * 20, 20)
+    r = registration_unif(pcd, gt, r3["T"], crop, 2 * tau, 20)
+    out = evaluate_histo(pcd, gt, r["T"], crop, tau / 2.0, tau)
+    out.update(dTau=tau, transformation=r["T"], registrations=(r2, r3, r))
+    return out
+
+
+# ---- trajectory alignment (host) ---------------------------------------------------------------------------------
+
+def _umeyama_points(src, dst):
+    n = src.shape[0]
+    ms, mt = src.sum(0) / n, dst.sum(0) / n
+    a, b = src - ms, dst - mt
+    return umeyama_from_sums(n, src.sum(0), dst.sum(0), a.T @ b, (a * a).sum())
+
+
+def trajectory_alignment(est_centers, gt_centers, gt_trans, generator, max_iteration=100000, max_distance=0.2,
+                         ransac_n=6):
+    """registration.py:66-110 on the host in numpy float64: camera centres est [n,3] onto gt [n,3] (moved by
+    the 4x4 gt_trans first, when given), paired index to index.  A seeded RANSAC: `ransac_n` pairs drawn by
+    `generator` (a numpy Generator), Umeyama with scale, inliers closer than `max_distance`, the best sample
+    by inlier count and then by inlier rmse, and a last estimate from its inliers.  open3d draws from a
+    generator of its own, so its samples (and a result to the last digit) cannot be reproduced; the rule can.
+    The loop stops early once a sample has every pair as an inlier.  -> 4x4 float64."""
+    est = np.asarray(est_centers, np.float64).reshape(-1, 3)
+    gt = np.asarray(gt_centers, np.float64).reshape(-1, 3)
+    if est.shape != gt.shape or est.shape[0] < ransac_n:
+        raise RuntimeError(f"trajectory_alignment: two [n, 3] sets of at least {ransac_n} centres "
+                           f"(got {est.shape}, {gt.shape})")
+    if gt_trans is not None:
+        G = np.asarray(gt_trans, np.float64).reshape(4, 4)
+        gt = gt @ G[:3, :3].T + G[:3, 3]
+    n = est.shape[0]
+    best, best_in = (-1, np.inf), None
+    for _ in range(int(max_iteration)):
+        pick = generator.choice(n, size=ransac_n, replace=False)
+        with np.errstate(all="ignore"):
+            T = _umeyama_points(est[pick], gt[pick])
+            d = np.linalg.norm(est @ T[:3, :3].T + T[:3, 3] - gt, axis=1)
+        inl = d < max_distance
+        k = int(inl.sum())
+        if k == 0:
+            continue
+        rmse = float(np.sqrt((d[inl] ** 2).sum() / k))
+        if k > best[0] or (k == best[0] and rmse < best[1]):
+            best, best_in = (k, rmse), inl
+        if k == n:
+            break
+    if best_in is None or best[0] < 3:
+        raise RuntimeError("trajectory_alignment: no sample had three inliers")
+    return _umeyama_points(est[best_in], gt[best_in])

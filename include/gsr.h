@@ -704,6 +704,96 @@ int gsr_points_nearest(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long 
                        const double* ref, double max_dist, double* dist, float* stage_ms, void* stream);
 
 /*
+ * Tanks and Temples F-score evaluation (the reference's eval_tnt/run.py, which
+ * is open3d on the CPU): the device half, in seven calls.  All points are
+ * float64 [n,3]; the arithmetic is float64 without contraction.  No float
+ * atomic is used, so every result is the same bits on every run.  Additive: the
+ * ABI version is unchanged.  A 4x4 `transform` is 16 host doubles, row-major;
+ * only its first three rows are read: p' = ((r0 x + r1 y) + r2 z) + t.
+ *
+ * gsr_points_crop_polygon (open3d SelectionPolygonVolume::CropInPolygon):
+ * `transform` (may be NULL) is applied first.  orthogonal_axis 0 / 1 / 2 = X /
+ * Y / Z gives the axes (u, v, w) = (1,2,0) / (0,2,1) / (0,1,2).  A point is
+ * dropped when p[w] < axis_min or p[w] > axis_max (both ends are kept).  For
+ * every edge (i, j = i + 1 mod M) of polygon [M,3] (host) with
+ * (b_i[v] < p[v] && b_j[v] >= p[v]) || (b_j[v] < p[v] && b_i[v] >= p[v]) the
+ * node is b_i[u] + (p[v] - b_i[v]) / (b_j[v] - b_i[v]) * (b_j[u] - b_i[u]); the
+ * point is kept iff the number of nodes strictly below p[u] is odd.  Outputs
+ * once their size is known: kept_alloc the ascending int64 positions [K],
+ * point_alloc the kept transformed points [K,3]; *num_kept = K.  scratch_alloc
+ * is called once (4 bytes per point plus a scan's temporary).  Limits:
+ * N < 2^31, M <= GSR_CROP_MAX_VERTICES (the polygon lives in LDS), else
+ * GSR_ERR_ARGS.  Synchronises `stream` once (K).  stage_ms: flags and scan,
+ * write.
+ *
+ * gsr_points_voxel_mean (open3d PointCloud::VoxelDownSample): origin =
+ * min_bound - 0.5 voxel, cell = floor((p - origin) / voxel) per axis, one
+ * output point per occupied cell = (the sum of its points in input order) /
+ * count.  open3d emits in hash-map order, which is no contract; here the cells
+ * come ascending in the packed key (cx, cy, cz), x most significant.  Outputs:
+ * mean_alloc means [C,3] float64, count_alloc counts [C] int64, cell_alloc
+ * cells [C,3] int64; *num_cells = C.  One lane walks one cell's run, however
+ * long.  scratch_alloc is called once (20 bytes per point plus the radix
+ * sort's temporary).  Limits: N < 2^31, a key of at most 64 bits, finite
+ * points, voxel > 0, else GSR_ERR_ARGS.  Synchronises `stream` twice (bounds;
+ * C).  stage_ms: bounds, keys, sort, heads and scan, emit.
+ *
+ * gsr_points_index_build / gsr_points_index_query: gsr_points_nearest in two
+ * halves.  build does the ref half once (bounds, density-derived grid, cell
+ * sort, gather) into `buffer`, a device block of the caller's of at least
+ * gsr_points_index_bytes(R) bytes (36 per point plus alignment), and describes
+ * it in *index (host).  There is no hidden state and nothing to free; the
+ * index holds a copy of ref's coordinates, and is valid while `buffer` is.
+ * query writes dist [Q] as gsr_points_nearest does (the same bits) and
+ * nearest [Q] int64: the position in the original ref of the nearest point
+ * with distance < max_dist, or -1 with +inf beyond.  Among equally near points
+ * the lowest position wins.  build calls scratch_alloc once (8 bytes per ref
+ * point plus the sort's temporary) and synchronises `stream` once (bounds);
+ * query calls it once (20 bytes per query plus the sort's temporary) and does
+ * not synchronise.  stage_ms: build bounds, ref sort; query query sort,
+ * search.
+ *
+ * gsr_icp_accumulate: the sums of point-to-point ICP over the pairs
+ * (src[i], ref[index[i]]) with index[i] >= 0; index [N] int64 in [-1, R).
+ * pass 1 -> sums[8] (host) = n, sum |s - t|^2, sum s (3), sum t (3).  pass 2
+ * takes means[6] (host; the caller's sum s / n, sum t / n) -> sums[10] =
+ * sum (s - m_s)(t - m_t)^T (9, row-major), sum |s - m_s|^2.  A fixed-shape
+ * tree reduction (a function of N alone).  scratch_alloc is called once
+ * (about 45 KB).  Synchronises `stream` once per pass.  stage_ms: sums.
+ *
+ * gsr_points_transform: points [N,3] <- transform, in place.  stage_ms:
+ * transform.
+ */
+#define GSR_CROP_MAX_VERTICES 1024
+typedef struct gsr_point_index {
+    long long R;         /* points indexed */
+    void* buffer;        /* the caller's device block */
+    double bounds_min[3], bounds_max[3];
+    double cell_size;
+    long long cells[3];  /* per axis */
+    int key_bits[3];
+} gsr_point_index;
+int gsr_points_crop_polygon(gsr_alloc_fn kept_alloc, void* kept_ctx, gsr_alloc_fn point_alloc, void* point_ctx,
+                            gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long N, const double* points,
+                            const double* transform, int orthogonal_axis, double axis_min, double axis_max,
+                            int num_vertices, const double* polygon, long long* num_kept, float* stage_ms,
+                            void* stream);
+int gsr_points_voxel_mean(gsr_alloc_fn mean_alloc, void* mean_ctx, gsr_alloc_fn count_alloc, void* count_ctx,
+                          gsr_alloc_fn cell_alloc, void* cell_ctx, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                          long long N, const double* points, double voxel, long long* num_cells, float* stage_ms,
+                          void* stream);
+size_t gsr_points_index_bytes(long long R);
+int gsr_points_index_build(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long R, const double* ref, void* buffer,
+                           size_t buffer_bytes, gsr_point_index* index, float* stage_ms, void* stream);
+int gsr_points_index_query(gsr_alloc_fn scratch_alloc, void* scratch_ctx, const gsr_point_index* index, long long Q,
+                           const double* query, double max_dist, double* dist, long long* nearest, float* stage_ms,
+                           void* stream);
+int gsr_icp_accumulate(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long N, const double* src, long long R,
+                       const double* ref, const long long* index, int pass, const double* means, double* sums,
+                       float* stage_ms, void* stream);
+int gsr_points_transform(long long N, double* points, const double* transform, float* stage_ms, void* stream);
+
+/*
  * Per-stage GPU timing (no reference equivalent; SURVEY §5 "tracing").  While
  * enabled, every kernel stage of the calls above is bracketed by two hipEvents
  * on the call's stream.  gsr_timing_collect() waits for the recorded events,
