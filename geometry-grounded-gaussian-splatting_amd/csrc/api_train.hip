@@ -1,6 +1,6 @@
 // api_train.hip — the C ABI (include/gsr.h) of the training step outside the rasteriser: the
 // optimiser and densification statistics, the colour gradients over views, the multi-view terms
-// (NCC, PatchMatch, SSIM, depth to normal), the parameter getters, the nearest-neighbour distance
+// (NCC, PatchMatch, SSIM, the fused photometric loss, depth to normal), the parameter getters, the nearest-neighbour distance
 // and the device-side densify / prune, 3D filter and opacity reset.  Host orchestration only.
 #include <vector>
 
@@ -223,6 +223,65 @@ int gsr_fused_ssim_backward(int NC, int H, int W, int valid, const float* img1, 
     hipError_t e = launch_ssim_bwd(NC, H, W, valid, img1, img2, factors, factors + plane, factors + 2 * plane,
                                    dL_dmean, dL_dimg1, (hipStream_t)stream_ptr);
     return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "fused_ssim backward", e);
+}
+
+// the argument checks the two photometric-loss entry points share; nullptr when they pass
+static const char* photo_check(int H, int W, int mode, int with_ssim, const float* image, const float* gt,
+                               const float* embedding, const float* gain, int top, int left, int Hc, int Wc) {
+    if (mode < kAppNo || mode > kAppGain) return "photo_loss: unknown appearance mode";
+    if (H <= 0 || W <= 0 || (with_ssim && (H <= 10 || W <= 10)))
+        return "photo_loss: invalid sizes (the SSIM needs H, W > 10)";
+    if (!image || !gt) return "photo_loss: missing image";
+    if ((mode == kAppGS || mode == kAppPGSR) && !embedding) return "photo_loss: this mode needs an embedding";
+    if (mode == kAppGain) {
+        if (!gain) return "photo_loss: the gain mode needs a gain plane";
+        if (top < 0 || left < 0 || Hc < 1 || Wc < 1 || Hc > H - top || Wc > W - left)
+            return "photo_loss: the crop lies outside the image";
+    }
+    return nullptr;
+}
+
+int gsr_photo_loss_forward(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int H, int W, int mode, int with_ssim,
+                           float lambda_dssim, const float* image, const float* gt, const float* mask,
+                           const float* bg, const float* embedding, const float* gain, int crop_top, int crop_left,
+                           int crop_h, int crop_w, float* out3, float* out_gt, float* factors, float* emb_sums,
+                           void* stream_ptr) {
+    if (const char* m = photo_check(H, W, mode, with_ssim, image, gt, embedding, gain, crop_top, crop_left, crop_h,
+                                    crop_w))
+        return fail(GSR_ERR_ARGS, m);
+    if (!out3 || !scratch_alloc) return fail(GSR_ERR_ARGS, "photo_loss: missing buffer");
+    void* buf = scratch_alloc(scratch_ctx, photo_loss_partials(H, W) * sizeof(float) + 256);
+    if (!buf) return fail(GSR_ERR_ALLOC, "photo_loss: scratch allocation failed");
+    float* partial = reinterpret_cast<float*>(aligned_base(buf));
+    const size_t plane = (size_t)3 * H * W;
+    if (!with_ssim) factors = nullptr;
+    if (mode != kAppGS && mode != kAppPGSR) emb_sums = nullptr;
+    const PhotoLossParams q{H, W, mode, with_ssim != 0, with_ssim ? lambda_dssim : 0.f, image, gt, mask, bg, embedding,
+                            gain, crop_top, crop_left, crop_h, crop_w};
+    hipError_t e = launch_photo_loss_fwd(q, out_gt, factors, factors ? factors + plane : nullptr,
+                                         factors ? factors + 2 * plane : nullptr, partial, out3, emb_sums,
+                                         (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "photo_loss forward", e);
+}
+
+int gsr_photo_loss_backward(int H, int W, int mode, int with_ssim, float lambda_dssim, const float* image,
+                            const float* gt, const float* mask, const float* bg, const float* embedding,
+                            const float* gain, int crop_top, int crop_left, int crop_h, int crop_w,
+                            const float* factors, const float* emb_sums, const float* dL_dloss, float* dL_dimage,
+                            float* dL_dembedding, float* dL_dgain, void* stream_ptr) {
+    if (const char* m = photo_check(H, W, mode, with_ssim, image, gt, embedding, gain, crop_top, crop_left, crop_h,
+                                    crop_w))
+        return fail(GSR_ERR_ARGS, m);
+    if (!dL_dloss || !dL_dimage || (with_ssim && !factors) || (dL_dembedding && !emb_sums))
+        return fail(GSR_ERR_ARGS, "photo_loss backward: missing buffer");
+    if (mode != kAppGS && mode != kAppPGSR) dL_dembedding = nullptr;
+    const size_t plane = (size_t)3 * H * W;
+    const PhotoLossParams q{H, W, mode, with_ssim != 0, with_ssim ? lambda_dssim : 0.f, image, gt, mask, bg, embedding,
+                            gain, crop_top, crop_left, crop_h, crop_w};
+    hipError_t e = launch_photo_loss_bwd(q, factors, with_ssim ? factors + plane : nullptr,
+                                         with_ssim ? factors + 2 * plane : nullptr, emb_sums, dL_dloss, dL_dimage,
+                                         dL_dembedding, dL_dgain, (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "photo_loss backward", e);
 }
 
 int gsr_depth_to_normal_forward(const float* depth, int H, int W, float Fx, float Fy, float Cx, float Cy,

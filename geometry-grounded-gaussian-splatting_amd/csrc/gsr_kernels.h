@@ -230,6 +230,21 @@ hipError_t launch_ssim_bwd(int NC, int H, int W, int valid, const float* img1, c
                            const float* fB, const float* fC, const float* dL_dloss, float* dL_dimg1,
                            hipStream_t stream);
 
+// photoloss.hip: the photometric loss (mask composite, appearance transform, L1 and D-SSIM) fused
+enum { kAppNo = 0, kAppGS = 1, kAppPGSR = 2, kAppGain = 3 };  // gsr_app_model (include/gsr.h)
+struct PhotoLossParams {
+    int H, W, mode, ssim;
+    float lambda;
+    const float *img, *gt, *mask, *bg, *emb, *gain;
+    int top, left, Hc, Wc;
+};
+size_t photo_loss_partials(int H, int W);
+hipError_t launch_photo_loss_fwd(const PhotoLossParams& q, float* out_gt, float* fA, float* fB, float* fC,
+                                 float* partial, float* out3, float* emb_sums, hipStream_t stream);
+hipError_t launch_photo_loss_bwd(const PhotoLossParams& q, const float* fA, const float* fB, const float* fC,
+                                 const float* emb_sums, const float* dL_dloss, float* dL_dimg, float* dL_demb,
+                                 float* dL_dgain, hipStream_t stream);
+
 // depth_normal.hip: normal map of a depth map and its backward
 hipError_t launch_depth_normal(bool backward, const float* depth, int H, int W, float Fx, float Fy, float Cx, float Cy,
                                const float* g, float* out, uint8_t* valid, hipStream_t stream);

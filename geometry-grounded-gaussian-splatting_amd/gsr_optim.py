@@ -156,7 +156,9 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
                 key = (beta1, beta2, group["eps"], float(st["step"]))
-                batches.setdefault(key, []).append(((p, p.grad, st["exp_avg"], st["exp_avg_sq"]), group["lr"]))
+                # (a convolution weight's gradient may come back in another memory format: same values, packed)
+                grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                batches.setdefault(key, []).append(((p, grad, st["exp_avg"], st["exp_avg_sq"]), group["lr"]))
         for (beta1, beta2, eps, step), items in batches.items():
             for k in range(0, len(items), _C.MAX_ADAM_GROUPS):
                 chunk = items[k:k + _C.MAX_ADAM_GROUPS]

@@ -5,7 +5,9 @@ kernels of this package: the end-to-end variant of SURVEY §8(d).
 Per iteration, in the reference's order:
   getters (gaussian_model.py:146-212, torch)  -> render() with require_depth
   (gaussian_renderer.render -> GaussianRasterizer, render_fwd.hip)
-  -> L1 (loss_utils.py:28-29; app_model NO)  -> depth_to_normal + normal loss
+  -> L1 (loss_utils.py:28-29; with fused_rgb_loss the mask composite, the
+  appearance model's L1 and the SSIM as one call, gsr_loss / photoloss.hip;
+  without it app_model NO and no mask only)  -> depth_to_normal + normal loss
   (train.py:171-176; depth_normal.hip)  -> PatchMatch (loss_utils.py:140-267:
   the median-depth points re-observed from the nearest camera through
   sample_depth (sample.hip), the geometric loss, warp_patch_ncc (ncc.hip) on
@@ -32,6 +34,7 @@ import torch
 import torch.nn.functional as F
 
 import gsr_densify
+import gsr_loss
 import gsr_scene as S
 from fused_ssim import fused_ssim
 from gaussian_renderer import render, sample_depth
@@ -61,6 +64,8 @@ class TrainView:
     Cy: float
     original_image: torch.Tensor | None = None
     gray_image: torch.Tensor | None = None
+    gt_mask: torch.Tensor | None = None
+    uid: int = 0
 
 
 def train_view(W: int, H: int, R: np.ndarray, T: np.ndarray, device) -> TrainView:
@@ -116,6 +121,55 @@ class TrainGaussians(torch.nn.Module):
         self.optimizer = FusedAdam([{"params": [p], "lr": lr, "name": nm} for nm, p, lr in groups], lr=0.0,
                                    eps=1e-15)
         self.percent_dense = 0.01  # OptimizationParams.percent_dense (arguments/__init__.py)
+        self.app_model = gsr_loss.AppModel.NO
+        self._appearance_embeddings = None
+        self.appearance_network = None
+
+    # ---- appearance models (gaussian_model.py:271-302, 383-448) ----
+    # OptimizationParams (arguments/__init__.py): the learning rates of the appearance groups
+    APP_LR = {"gs_init": 0.01, "gs_final": 0.001, "gs_delay_steps": 0, "gs_delay_mult": 0.0, "iterations": 30000,
+              "embeddings": 0.001, "network": 0.001, "pgsr": 0.001}
+
+    def create_app_model(self, num_cameras: int, app_model, lr: dict | None = None) -> None:
+        """The per-view appearance parameters with the reference's initial
+        values, added to the optimizer under its group names
+        ("appearance_embeddings", and "appearance_network" for GOF); `lr`
+        overrides entries of APP_LR."""
+        if self._appearance_embeddings is not None:
+            raise RuntimeError("create_app_model: the appearance model is already set")
+        name = gsr_loss.app_model_name(app_model)
+        self.app_model = gsr_loss.AppModel(name)
+        dev = self._xyz.device
+        a = {**self.APP_LR, **(lr or {})}
+        if name == "no":
+            return
+        if name == "gs":
+            emb = torch.eye(3, 4, device=dev).expand(num_cameras, -1, -1).clone()
+            group_lr = a["gs_init"]
+            self.exposure_scheduler_args = _expon_lr(a["gs_init"], a["gs_final"], a["gs_delay_steps"],
+                                                     a["gs_delay_mult"], a["iterations"])
+        elif name == "gof":
+            self.appearance_network = gsr_loss.AppearanceNetwork(3 + 64, 3).to(dev)
+            emb = torch.empty(num_cameras, 64, device=dev).normal_(0, 1e-4)
+            group_lr = a["embeddings"]
+        else:
+            emb = torch.zeros(num_cameras, 2, device=dev)
+            group_lr = a["pgsr"]  # (the reference's "beta" entry of this group is not a key Adam reads)
+        self._appearance_embeddings = torch.nn.Parameter(emb)
+        self.optimizer.add_param_group({"params": [self._appearance_embeddings], "lr": group_lr,
+                                        "name": "appearance_embeddings"})
+        if name == "gof":
+            self.optimizer.add_param_group({"params": list(self.appearance_network.parameters()),
+                                            "lr": a["network"], "name": "appearance_network"})
+
+    def get_apperance_embedding(self, idx):
+        return self._appearance_embeddings[idx]
+
+    def update_learning_rate(self, iteration):
+        """The exposure schedule of the GS appearance model (gaussian_model.py:447-448)."""
+        for group in self.optimizer.param_groups:
+            if group["name"] == "appearance_embeddings" and self.app_model is gsr_loss.AppModel.GS:
+                group["lr"] = self.exposure_scheduler_args(iteration)
 
     # ---- densification (gaussian_model.py:220-262, 521-539, 797-816; gsr_densify, densify.hip) ----
     def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size=None, *, noise=None, generator=None):
@@ -207,6 +261,23 @@ class TrainGaussians(torch.nn.Module):
     @property
     def get_sg_color(self):
         return self._sg_color
+
+
+def _expon_lr(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
+    """utils/general_utils.py get_expon_lr_func: log-linear from lr_init to
+    lr_final over max_steps, scaled by a sine ramp from lr_delay_mult during
+    the first lr_delay_steps."""
+
+    def fn(step):
+        if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            return 0.0
+        delay = 1.0
+        if lr_delay_steps > 0:
+            delay = lr_delay_mult + (1 - lr_delay_mult) * math.sin(0.5 * math.pi * min(max(step / lr_delay_steps, 0), 1))
+        t = min(max(step / max_steps, 0), 1)
+        return delay * math.exp(math.log(lr_init) * (1 - t) + math.log(lr_final) * t)
+
+    return fn
 
 
 class _Pipe:
@@ -325,8 +396,13 @@ class TrainStep:
     COMPONENTS = ("render", "depth_normal", "patchmatch", "rgb_loss", "backward", "densify_stats", "adam")
 
     def __init__(self, gaussians: TrainGaussians, kernel_size: float = 0.0, bg=None, densify: bool = True,
-                 fused_patchmatch: bool = True):
+                 fused_patchmatch: bool = True, fused_rgb_loss: bool = False):
         self.g = gaussians
+        # the photometric term as one fused call (gsr_loss.rgb_loss: the view's mask, the appearance model),
+        # or the L1 and fused_ssim of app_model NO without a mask
+        self.fused_rgb_loss = fused_rgb_loss
+        if not fused_rgb_loss and gaussians.app_model is not gsr_loss.AppModel.NO:
+            raise RuntimeError("TrainStep: an appearance model needs fused_rgb_loss=True")
         # PatchMatch on the fused kernels (gsr_patchmatch), or the reference's torch formulation (patchmatch)
         self.patchmatch = patchmatch_fused if fused_patchmatch else patchmatch
         self.kernel_size = kernel_size
@@ -364,9 +440,14 @@ class TrainStep:
         ncc_loss, geo_loss = self.patchmatch(g, pkg, view, nearest, self.kernel_size, self.pipe)
         self._mark()
         gt = view.original_image
-        l1 = torch.abs(image - gt).mean()
-        rgb_loss = (1.0 - LAMBDA_DSSIM) * l1 + LAMBDA_DSSIM * (1.0 - fused_ssim(image.unsqueeze(0), gt.unsqueeze(0),
-                                                                                 padding="valid"))
+        if self.fused_rgb_loss:
+            rgb_loss = self._fused_rgb_loss(g, view, image, gt)
+        elif g.app_model is not gsr_loss.AppModel.NO or view.gt_mask is not None:
+            raise RuntimeError("TrainStep: an appearance model or a masked view needs fused_rgb_loss=True")
+        else:
+            l1 = torch.abs(image - gt).mean()
+            rgb_loss = (1.0 - LAMBDA_DSSIM) * l1 + LAMBDA_DSSIM * (1.0 - fused_ssim(image.unsqueeze(0),
+                                                                                     gt.unsqueeze(0), padding="valid"))
         loss = rgb_loss + LAMBDA_DEPTH_NORMAL * normal_loss + LAMBDA_NCC * ncc_loss + LAMBDA_GEO * geo_loss
         self._mark()
         loss.backward()
@@ -379,6 +460,19 @@ class TrainStep:
             g.optimizer.zero_grad(set_to_none=True)
         self._mark()
         return loss.detach()
+
+    def _fused_rgb_loss(self, g, view, image, gt):
+        # train.py:159-169, 189 as one call; GOF's network runs in torch and hands the kernel its gain
+        name = g.app_model.value
+        kw = {}
+        if name == "gof":
+            kw["gain"], kw["crop"] = gsr_loss.gof_gain(image, g.get_apperance_embedding(view.uid),
+                                                        g.appearance_network)
+            name = "gain"
+        elif name != "no":
+            kw["embedding"] = g.get_apperance_embedding(view.uid)
+        return gsr_loss.rgb_loss(image, gt, mask=view.gt_mask, bg=self.bg, app_model=name,
+                                 lambda_dssim=LAMBDA_DSSIM, **kw)[0]
 
     def component_ms(self) -> dict:
         """Milliseconds per component of the last timed step (synchronises)."""

@@ -482,6 +482,41 @@ int gsr_fused_ssim_backward(int NC, int H, int W, int valid, const float* img1, 
                             const float* factors, const float* dL_dmean, float* dL_dimg1, void* stream);
 
 /*
+ * Photometric loss, fused: the first term of the reference's training loss
+ * as its geometry pipelines compute it (train.py:159-169, 189;
+ * utils/loss_utils.py:90-123).  image, gt: [3,H,W] fp32.
+ *   g_c = mask ? (mask[p] > 0.5 ? gt_c : bg_c) : gt_c   (mask [H,W], strict;
+ *         bg [3], NULL = black)
+ *   t_c = the appearance transform of the rendered image (gsr_app_model):
+ *         NO x_c; GS E[c,3] + sum_k E[c,k] x_k (embedding [3,4]); PGSR
+ *         e[1] + exp(e[0]) x_c (embedding [2]); GAIN gain_c[p] x_c inside the
+ *         crop (gain [3,crop_h,crop_w] contiguous; the L1 over the crop only)
+ *   out3 = {(1 - lambda) l1 + lambda (1 - ssim), l1 = mean|t - g|, ssim}
+ * with ssim the "valid" mean SSIM of the raw image against g (the arithmetic
+ * of gsr_fused_ssim_forward).  with_ssim == 0: the L1 alone (any H, W >= 1;
+ * out3 = {l1, l1, 0}, lambda ignored).  out_gt (NULL or [3,H,W]) receives g.
+ * factors (NULL or 3*3*H*W floats) and emb_sums (NULL, or 12 floats for GS, 2
+ * for PGSR) receive what the backward reads; both NULL when no gradient is
+ * wanted.  One stencil launch and one fixed-order reduction: two runs give
+ * the same bits.  The backward is one launch: dL/dimage [3,H,W], and where
+ * asked dL/dembedding (the embedding's shape) and dL/dgain (the gain's),
+ * for dL/d out3[0] at dL_dloss (device scalar).
+ * GSR_ERR_ARGS before any launch: unknown mode, a mode's buffer missing, a
+ * crop outside the image, H or W <= 10 with the SSIM on.
+ */
+enum gsr_app_model { GSR_APP_NO = 0, GSR_APP_GS = 1, GSR_APP_PGSR = 2, GSR_APP_GAIN = 3 };
+int gsr_photo_loss_forward(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int H, int W, int mode, int with_ssim,
+                           float lambda_dssim, const float* image, const float* gt, const float* mask,
+                           const float* bg, const float* embedding, const float* gain, int crop_top, int crop_left,
+                           int crop_h, int crop_w, float* out3, float* out_gt, float* factors, float* emb_sums,
+                           void* stream);
+int gsr_photo_loss_backward(int H, int W, int mode, int with_ssim, float lambda_dssim, const float* image,
+                            const float* gt, const float* mask, const float* bg, const float* embedding,
+                            const float* gain, int crop_top, int crop_left, int crop_h, int crop_w,
+                            const float* factors, const float* emb_sums, const float* dL_dloss, float* dL_dimage,
+                            float* dL_dembedding, float* dL_dgain, void* stream);
+
+/*
  * Depth-normal consistency input: replaces the torch
  * function depth_to_normal (utils/graphics_utils.py:103-119).  depth [H,W];
  * forward: normal [3,H,W] (zero on the border), valid [H,W] uint8;
