@@ -1,6 +1,7 @@
 // api_tnt.hip — the C ABI (include/gsr.h) of the TnT F-score evaluation (tnteval.hip): polygon crop,
-// voxel-mean grid, nearest-point index (build / query), ICP sums, in-place transform.  Host
-// orchestration only.
+// voxel-mean grid, nearest-point index (build / query), ICP sums, in-place transform; and of the mesh
+// culling that precedes it (meshraster.hip): triangle depth raster and view vote.  Host orchestration
+// only.
 #include <float.h>
 #include <math.h>
 #include <string.h>
@@ -26,6 +27,92 @@ PointGrid index_grid(const gsr_point_index& ix) {
     g.bx = ix.key_bits[0], g.by = ix.key_bits[1], g.bz = ix.key_bits[2];
     g.hashed = 0;
     return g;
+}
+
+// Per-stage GPU times summed over the views of one call: StageTimes holds one event pair per stage, a
+// loop over views needs one per stage and view.  Measurement only; with stage_ms NULL nothing is created.
+class ViewStageTimes {
+  public:
+    ViewStageTimes(float* stage_ms, hipStream_t stream) : ms_(stage_ms), stream_(stream) {
+        if (ms_)
+            for (int k = 0; k < 8; k++) ms_[k] = 0.f;
+    }
+    ViewStageTimes(const ViewStageTimes&) = delete;
+    ViewStageTimes& operator=(const ViewStageTimes&) = delete;
+    hipError_t begin(int k) {
+        if (!ms_) return hipSuccess;
+        Span sp{k, nullptr, nullptr};
+        hipError_t e = hipEventCreate(&sp.a);
+        if (e == hipSuccess) e = hipEventCreate(&sp.b);
+        spans_.push_back(sp);
+        return e == hipSuccess ? hipEventRecord(sp.a, stream_) : e;
+    }
+    hipError_t end(int) { return ms_ ? hipEventRecord(spans_.back().b, stream_) : hipSuccess; }
+    hipError_t collect() {
+        if (!ms_) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(stream_);
+        for (size_t k = 0; k < spans_.size() && e == hipSuccess; k++) {
+            float t = 0.f;
+            e = hipEventElapsedTime(&t, spans_[k].a, spans_[k].b);
+            ms_[spans_[k].stage] += t;
+        }
+        return e;
+    }
+    ~ViewStageTimes() {
+        for (auto& sp : spans_) {
+            if (sp.a) (void)hipEventDestroy(sp.a);
+            if (sp.b) (void)hipEventDestroy(sp.b);
+        }
+    }
+
+  private:
+    struct Span {
+        int stage;
+        hipEvent_t a, b;
+    };
+    float* ms_;
+    hipStream_t stream_;
+    std::vector<Span> spans_;
+};
+
+int raster_camera(const char* who, const float* w2c, int H, int W, float fx, float fy, float cx, float cy, float znear,
+                  float zfar, RasterCamera& c) {
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(GSR_ERR_ARGS, who);
+    const float v[6] = {fx, fy, cx, cy, znear, zfar};
+    for (float x : v)
+        if (!(x > -FLT_MAX && x < FLT_MAX)) return fail(GSR_ERR_ARGS, who);
+    if (!(fx > 0.f && fy > 0.f && znear > 0.f && zfar >= znear)) return fail(GSR_ERR_ARGS, who);
+    if (w2c) memcpy(c.m, w2c, sizeof(c.m));
+    c.fx = fx, c.fy = fy, c.cx = cx, c.cy = cy, c.znear = znear, c.zfar = zfar, c.W = W, c.H = H;
+    return GSR_OK;
+}
+
+// the stages of one view's depth map into s.depth (stages 0-3 of `times`)
+template <class Times>
+int raster_view(Times& times, const RasterCamera& c, long long V, const float* vertices, long long F, const void* faces,
+                bool is64, bool count, const MeshRasterState& s, hipStream_t stream) {
+    GSR_TIMED(times, 0, launch_raster_clear(c, s, stream), "depth clear");
+    if (F == 0) return GSR_OK;
+    GSR_TIMED(times, 1, launch_raster_setup(c, V, F, vertices, faces, is64, count, s, stream), "raster set-up");
+    GSR_TIMED(times, 2, launch_raster_scan(F, s, stream), "unit scan");
+    GSR_TIMED(times, 3, launch_raster_units(c, V, F, vertices, faces, is64, count, s, stream), "raster units");
+    return GSR_OK;
+}
+
+// the one readback of a raster call: the vertex id flag, and the counters when asked for
+int raster_readback(const char* who, const MeshRasterState& s, unsigned long long* counters, hipStream_t stream) {
+    Readback rb;
+    GSR_CHECK(rb.begin(stream), "pinned readback buffer");
+    GSR_CHECK(rb.copy(0, s.bad, sizeof(uint32_t)), "memcpy vertex id flag");
+    GSR_CHECK(rb.commit(), "event record");
+    if (counters)
+        GSR_CHECK(hipMemcpyAsync(counters, s.counters, kRasterCounters * sizeof(unsigned long long),
+                                 hipMemcpyDeviceToHost, stream),
+                  "memcpy counters");
+    GSR_CHECK(rb.wait(), "event sync");
+    if (counters) GSR_CHECK(hipStreamSynchronize(stream), "stream sync");
+    if (rb[0]) return fail(GSR_ERR_ARGS, who);
+    return GSR_OK;
 }
 
 }  // namespace
@@ -274,6 +361,80 @@ int gsr_points_transform(long long N, double* points, const double* transform, f
     if (N >= 0x80000000ll) return fail(GSR_ERR_ARGS, "points_transform: 2^31 or more points");
     if (!points) return fail(GSR_ERR_ARGS, "points_transform: missing buffer");
     GSR_TIMED(times, 0, launch_points_transform(N, points, transform, stream), "transform");
+    GSR_CHECK(times.collect(), "stage times");
+    return GSR_OK;
+}
+
+int gsr_mesh_depth(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long V, const float* vertices, long long F,
+                   const void* faces, int faces_int64, const float* w2c, int H, int W, float fx, float fy, float cx,
+                   float cy, float znear, float zfar, float* depth, unsigned long long* counters, float* stage_ms,
+                   void* stream_ptr) {
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    StageTimes times(stage_ms, stream);
+    if (counters)
+        for (int k = 0; k < kRasterCounters; k++) counters[k] = 0;
+    if (V < 0 || F < 0) return fail(GSR_ERR_ARGS, "mesh_depth: negative size");
+    if (V >= 0x80000000ll || F >= 0x80000000ll) return fail(GSR_ERR_ARGS, "mesh_depth: 2^31 or more elements");
+    RasterCamera c{};
+    if (!w2c || !depth) return fail(GSR_ERR_ARGS, "mesh_depth: missing buffer");
+    if (int rc = raster_camera("mesh_depth: image size, intrinsics or depth range out of range", w2c, H, W, fx, fy, cx,
+                               cy, znear, zfar, c))
+        return rc;
+    if (F == 0) {
+        GSR_CHECK(hipMemsetAsync(depth, 0, (size_t)H * (size_t)W * sizeof(float), stream), "depth clear");
+        return GSR_OK;
+    }
+    if (!faces || (V > 0 && !vertices)) return fail(GSR_ERR_ARGS, "mesh_depth: missing buffer");
+    if (!scratch_alloc) return fail(GSR_ERR_ARGS, "mesh_depth: missing allocator");
+    MeshRasterState s;
+    if (int rc = carve_alloc(scratch_alloc, scratch_ctx, "mesh_depth: scratch allocation failed", carve_mesh_raster, F,
+                             H, W, s))
+        return rc;
+    GSR_CHECK(launch_raster_reset(s, stream), "raster reset");
+    if (int rc = raster_view(times, c, V, vertices, F, faces, faces_int64 != 0, counters != nullptr, s, stream))
+        return rc;
+    GSR_TIMED(times, 4, launch_raster_finish(c, s, depth, stream), "depth finish");
+    if (int rc = raster_readback("mesh_depth: a face names a vertex outside [0, V)", s, counters, stream)) return rc;
+    GSR_CHECK(times.collect(), "stage times");
+    return GSR_OK;
+}
+
+int gsr_mesh_view_votes(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long V, const float* vertices, long long F,
+                        const void* faces, int faces_int64, int n_views, const float* w2cs, int H, int W, float fx,
+                        float fy, float cx, float cy, float znear, float zfar, float eps, int* counts,
+                        unsigned long long* counters, float* stage_ms, void* stream_ptr) {
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    ViewStageTimes times(stage_ms, stream);
+    if (counters)
+        for (int k = 0; k < kRasterCounters; k++) counters[k] = 0;
+    if (V < 0 || F < 0 || n_views < 0) return fail(GSR_ERR_ARGS, "mesh_view_votes: negative size");
+    if (V >= 0x80000000ll || F >= 0x80000000ll)
+        return fail(GSR_ERR_ARGS, "mesh_view_votes: 2^31 or more elements");
+    RasterCamera c{};
+    if (int rc = raster_camera("mesh_view_votes: image size, intrinsics or depth range out of range", nullptr, H, W,
+                               fx, fy, cx, cy, znear, zfar, c))
+        return rc;
+    if (!(eps > -FLT_MAX && eps < FLT_MAX)) return fail(GSR_ERR_ARGS, "mesh_view_votes: eps must be finite");
+    if (V == 0 && F == 0) return GSR_OK;
+    if ((V > 0 && (!vertices || !counts)) || (F > 0 && !faces) || (n_views > 0 && !w2cs))
+        return fail(GSR_ERR_ARGS, "mesh_view_votes: missing buffer");
+    if (V > 0) GSR_CHECK(hipMemsetAsync(counts, 0, (size_t)V * sizeof(int), stream), "count clear");
+    if (n_views == 0) return GSR_OK;
+    if (!scratch_alloc) return fail(GSR_ERR_ARGS, "mesh_view_votes: missing allocator");
+    MeshRasterState s;
+    if (int rc = carve_alloc(scratch_alloc, scratch_ctx, "mesh_view_votes: scratch allocation failed",
+                             carve_mesh_raster, F, H, W, s))
+        return rc;
+    GSR_CHECK(launch_raster_reset(s, stream), "raster reset");
+    // every view on the stream, one depth buffer, nothing read back in between
+    for (int k = 0; k < n_views; k++) {
+        memcpy(c.m, w2cs + 12 * (size_t)k, sizeof(c.m));
+        if (int rc = raster_view(times, c, V, vertices, F, faces, faces_int64 != 0, counters != nullptr, s, stream))
+            return rc;
+        if (V > 0) GSR_TIMED(times, 4, launch_view_vote(c, eps, V, vertices, s, counts, stream), "view vote");
+    }
+    if (int rc = raster_readback("mesh_view_votes: a face names a vertex outside [0, V)", s, counters, stream))
+        return rc;
     GSR_CHECK(times.collect(), "stage times");
     return GSR_OK;
 }

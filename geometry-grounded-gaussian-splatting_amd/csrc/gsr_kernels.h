@@ -536,6 +536,41 @@ hipError_t launch_icp_accumulate(int pass, long long N, const double* src, long 
                                  const long long* index, const double* means6, const IcpState& s, hipStream_t stream);
 hipError_t launch_points_transform(long long N, double* points, const double* T12, hipStream_t stream);
 
+// TnT mesh culling (meshraster.hip): triangle depth raster of one pinhole view and the per-vertex view vote.
+// Scratch: 4 bytes per pixel, 12 per triangle and the scan's temporary.
+constexpr int kRasterLanePixels = 32;      // a screen bound of at most this many centres: one lane
+constexpr int kRasterTile = 64;            // beyond: one wave per kRasterTile x kRasterTile tile of the bound
+constexpr int kRasterUnitBlocks = 2048;    // the fixed grid of the wave kernel (4 waves per block)
+constexpr uint32_t kRasterEmpty = 0xFFFFFFFFu;  // a depth word no triangle has reached
+constexpr int kRasterCounters = 4;         // atomics issued, centres tested, lane triangles, wave units
+struct RasterCamera {  // by value into the kernels
+    float m[12];       // the first three rows of the world -> camera matrix
+    float fx, fy, cx, cy, znear, zfar;
+    int W, H;
+};
+struct MeshRasterState {
+    uint32_t* depth;              // [H W] depth bit patterns, kRasterEmpty where nothing was drawn
+    uint32_t* units;              // [F + 1] wave units per triangle (0: drawn by its lane, or nothing to draw)
+    unsigned long long* offsets;  // [F + 1] their exclusive scan: offsets[F] = the number of units
+    uint32_t* bad;                // a face names a vertex outside [0, V)
+    unsigned long long* counters;  // [kRasterCounters] (measurement only)
+    void* tmp;
+    size_t tmp_bytes;
+};
+size_t carve_mesh_raster(void* base, long long F, int H, int W, MeshRasterState& s);
+hipError_t launch_raster_reset(const MeshRasterState& s, hipStream_t stream);
+hipError_t launch_raster_clear(const RasterCamera& c, const MeshRasterState& s, hipStream_t stream);
+hipError_t launch_raster_setup(const RasterCamera& c, long long V, long long F, const float* vertices,
+                               const void* faces, bool is64, bool count, const MeshRasterState& s,
+                               hipStream_t stream);
+hipError_t launch_raster_scan(long long F, const MeshRasterState& s, hipStream_t stream);
+hipError_t launch_raster_units(const RasterCamera& c, long long V, long long F, const float* vertices,
+                               const void* faces, bool is64, bool count, const MeshRasterState& s,
+                               hipStream_t stream);
+hipError_t launch_raster_finish(const RasterCamera& c, const MeshRasterState& s, float* depth, hipStream_t stream);
+hipError_t launch_view_vote(const RasterCamera& c, float eps, long long V, const float* vertices,
+                            const MeshRasterState& s, int* counts, hipStream_t stream);
+
 // densify.hip: densify / prune plan and gather, radix-select quantile, 3D filter, opacity reset
 constexpr int kMaxDensifyParams = 16;
 enum : int { kDensifyCopy = 0, kDensifyXyz = 1, kDensifyScaling = 2 };

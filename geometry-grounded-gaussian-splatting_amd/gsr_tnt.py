@@ -7,6 +7,13 @@ _query, gsr_icp_accumulate, gsr_points_transform; csrc/tnteval.hip); the 3x3
 SVD of each ICP update, the readers and the camera-centre RANSAC on the host in
 numpy float64.  All geometry is float64.
 
+The step before it, eval_tnt/cull_mesh.py (pyrender depth maps and a per-vertex
+view vote), is here too: render_mesh_depth, mesh_view_votes and cull_mesh over
+gsr_mesh_depth / gsr_mesh_view_votes (csrc/meshraster.hip), float32 as the
+reference's vote is.
+
+    vertices, faces = cull_mesh(vertices, faces, read_cull_trajectory("Barn_COLMAP_SfM.log"))
+
     crop = read_crop_volume("Barn.json")
     init = trajectory_alignment(est_centers, gt_centers, gt_trans, np.random.default_rng(0))
     out = tnt_fscore(vertices, faces, gt_points, crop, init, SCENES_TAU["Barn"])
@@ -40,6 +47,8 @@ BUILD_STAGES = ("bounds", "ref_sort")
 QUERY_STAGES = ("query_sort", "search")
 ICP_STAGES = ("sums",)
 TRANSFORM_STAGES = ("transform",)
+RASTER_STAGES = ("clear", "setup_small", "unit_scan", "wave_units", "finish_or_vote")
+RASTER_COUNTERS = ("atomics", "centres_tested", "lane_triangles", "wave_units")
 _AXIS = {"X": 0, "Y": 1, "Z": 2}
 measure_stages = False
 
@@ -70,6 +79,11 @@ def _lib():
         L.gsr_icp_accumulate.argtypes = [A, vp, ll, vp, ll, vp, vp, i, dp, dp, fp, vp]
         L.gsr_points_transform.restype = i
         L.gsr_points_transform.argtypes = [ll, vp, dp, fp, vp]
+        f, up = ctypes.c_float, ctypes.POINTER(ctypes.c_ulonglong)
+        L.gsr_mesh_depth.restype = i
+        L.gsr_mesh_depth.argtypes = [A, vp, ll, vp, ll, vp, i, fp, i, i, f, f, f, f, f, f, vp, up, fp, vp]
+        L.gsr_mesh_view_votes.restype = i
+        L.gsr_mesh_view_votes.argtypes = [A, vp, ll, vp, ll, vp, i, i, fp, i, i, f, f, f, f, f, f, f, vp, up, fp, vp]
         L._tnteval_bound = True
     return L
 
@@ -446,6 +460,116 @@ def tnt_fscore(vertices, faces, gt_points, crop, init_T, tau):
     out = evaluate_histo(pcd, gt, r["T"], crop, tau / 2.0, tau)
     out.update(dTau=tau, transformation=r["T"], registrations=(r2, r3, r))
     return out
+
+
+# ---- mesh culling (cull_mesh.py) ---------------------------------------------------------------------------------
+
+def _w2c_rows(w2c, who, batched):
+    """World -> camera matrices, 4x4 or 3x4, as contiguous float32 [n,3,4] on the host."""
+    m = np.asarray(w2c.detach().cpu().numpy() if isinstance(w2c, torch.Tensor) else w2c, dtype=np.float64)
+    if not batched:
+        m = m[None]
+    if m.ndim != 3 or m.shape[1:] not in ((4, 4), (3, 4)):
+        raise RuntimeError(f"{who}: a camera matrix must have shape (4, 4) or (3, 4) (got {m.shape[1:]})")
+    return np.ascontiguousarray(m[:, :3, :].astype(np.float32))
+
+
+def _mesh_args(vertices, faces, who):
+    _require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
+    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
+    if vertices.size(1) != 3 or faces.size(1) != 3 or faces.device != vertices.device:
+        raise RuntimeError(f"{who}: `vertices` and `faces` must have shapes (V, 3) and (F, 3) on one device")
+    return vertices.to(torch.float32).contiguous(), faces.contiguous()
+
+
+def _fptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+@torch.no_grad()
+def render_mesh_depth(vertices, faces, w2c, H, W, fx, fy, cx, cy, znear=0.01, zfar=20.0, count=False):
+    """The depth map of a triangle mesh from one OpenCV pinhole camera (x right, y down, z forward; w2c 4x4 or
+    3x4 world -> camera): depth [H,W] float32 = the smallest camera-space z in [znear, zfar] under each pixel
+    centre (j + 0.5, i + 0.5), 0 where no triangle lies.  Both facings count.  vertices [V,3] float32 / float64
+    (rendered as float32), faces [F,3] int32 / int64.  -> (depth, stats); stats["counters"] with `count`."""
+    who = "render_mesh_depth"
+    v, f = _mesh_args(vertices, faces, who)
+    dev = v.device
+    m = _w2c_rows(w2c, who, False)
+    depth = torch.empty(int(H), int(W), dtype=torch.float32, device=dev)
+    L = _lib()
+    scratch, ms = _G._ScratchBlocks(dev), _ms()
+    ctr = (ctypes.c_ulonglong * 4)() if count else None
+    with torch.cuda.device(dev):
+        rc = L.gsr_mesh_depth(scratch.cb, None, v.size(0), _G._ptr(v), f.size(0), _G._ptr(f),
+                              1 if f.dtype == torch.int64 else 0, _fptr(m), int(H), int(W), fx, fy, cx, cy, znear,
+                              zfar, _G._ptr(depth), ctr, ms, _G._stream(dev))
+    _check(L, rc)
+    return depth, _stats(RASTER_STAGES, ms, scratch, counters=None if ctr is None else dict(zip(RASTER_COUNTERS, ctr)))
+
+
+@torch.no_grad()
+def mesh_view_votes(vertices, faces, w2cs, H, W, fx, fy, cx, cy, znear=0.01, zfar=20.0, eps=0.005, count=False):
+    """cull_mesh.py's point_masks over depth maps rendered here: counts [V] int32 = the number of the views
+    w2cs [n,4,4] / [n,3,4] in which the vertex is inside the frustum (0 <= u <= W - 1, 0 <= v <= H - 1, z > 0)
+    and not more than eps behind the view's depth map, sampled bilinearly at (u, v).  One depth buffer serves
+    every view and nothing but the counts leaves the device.  -> (counts, stats)."""
+    who = "mesh_view_votes"
+    v, f = _mesh_args(vertices, faces, who)
+    dev = v.device
+    m = _w2c_rows(w2cs, who, True)
+    counts = torch.empty(v.size(0), dtype=torch.int32, device=dev)
+    L = _lib()
+    scratch, ms = _G._ScratchBlocks(dev), _ms()
+    ctr = (ctypes.c_ulonglong * 4)() if count else None
+    with torch.cuda.device(dev):
+        rc = L.gsr_mesh_view_votes(scratch.cb, None, v.size(0), _G._ptr(v), f.size(0), _G._ptr(f),
+                                   1 if f.dtype == torch.int64 else 0, m.shape[0], _fptr(m), int(H), int(W), fx, fy,
+                                   cx, cy, znear, zfar, eps, _G._ptr(counts), ctr, ms, _G._stream(dev))
+    _check(L, rc)
+    return counts, _stats(RASTER_STAGES, ms, scratch,
+                          counters=None if ctr is None else dict(zip(RASTER_COUNTERS, ctr)))
+
+
+def read_cull_trajectory(path):
+    """Camera-to-world poses for cull_mesh: a .log trajectory (read_trajectory) or an .npy of [n,4,4] / [n,3,4]
+    matrices -> [n,4,4] float64."""
+    if str(path).endswith(".npy"):
+        m = np.asarray(np.load(path), dtype=np.float64)
+        if m.ndim != 3 or m.shape[1:] not in ((4, 4), (3, 4)):
+            raise RuntimeError(f"read_cull_trajectory: {path}: expected [n,4,4] or [n,3,4] (got {m.shape})")
+        out = np.tile(np.eye(4), (m.shape[0], 1, 1))
+        out[:, :m.shape[1], :] = m
+        return out
+    if str(path).endswith(".log"):
+        return read_trajectory(path)[1]
+    raise RuntimeError(f"read_cull_trajectory: {path}: a .log or .npy trajectory (the .json branch is not built)")
+
+
+@torch.no_grad()
+def cull_mesh(vertices, faces, c2ws, H=1080, W=1920, fx=1163.8678928442187, fy=1172.793101201448,
+              cx=962.3120628412543, cy=542.0667209577691, far=20.0, min_views=20, eps=0.005):
+    """cull_mesh.py: keep the vertices that at least `min_views` of the cameras c2ws [n,4,4] / [n,3,4] (camera
+    -> world, inverted here in float64) see, the faces whose three corners are kept, and of the kept vertices
+    those a kept face names; the surviving order is preserved.  The defaults are the reference's TnT
+    intrinsics.  -> (vertices', faces' int64)."""
+    who = "cull_mesh"
+    _mesh_args(vertices, faces, who)
+    c = np.asarray(c2ws.detach().cpu().numpy() if isinstance(c2ws, torch.Tensor) else c2ws, dtype=np.float64)
+    if c.ndim != 3 or c.shape[1:] not in ((4, 4), (3, 4)):
+        raise RuntimeError(f"{who}: `c2ws` must have shape (n, 4, 4) or (n, 3, 4) (got {c.shape})")
+    full = np.tile(np.eye(4), (c.shape[0], 1, 1))
+    full[:, :c.shape[1], :] = c
+    w2cs = np.linalg.inv(full) if c.shape[0] else full
+    counts, _ = mesh_view_votes(vertices, faces, w2cs, H, W, fx, fy, cx, cy, 0.01, far, eps)
+    keep_v = counts >= int(min_views)
+    f = faces.long()
+    keep_f = keep_v[f[:, 0]] & keep_v[f[:, 1]] & keep_v[f[:, 2]]
+    f = f[keep_f]
+    used = torch.zeros(vertices.size(0), dtype=torch.bool, device=vertices.device)
+    used[f.reshape(-1)] = True
+    remap = torch.cumsum(used.to(torch.int64), 0) - 1
+    return vertices[used], remap[f]
 
 
 # ---- trajectory alignment (host) ---------------------------------------------------------------------------------

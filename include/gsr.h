@@ -829,6 +829,50 @@ int gsr_icp_accumulate(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long 
 int gsr_points_transform(long long N, double* points, const double* transform, float* stage_ms, void* stream);
 
 /*
+ * Tanks and Temples mesh culling (the reference's eval_tnt/cull_mesh.py, which
+ * renders with pyrender / OpenGL): the depth map of a triangle mesh from one
+ * pinhole view, and the per-vertex count of the views that see a vertex.
+ * vertices [V,3] float32 and faces [F,3] int32 or int64 (faces_int64) are device
+ * memory; w2c / w2cs are HOST float32, one row-major 3x4 world -> camera matrix
+ * per view (x right, y down, z forward).
+ *
+ * gsr_mesh_depth: depth [H,W] float32 (device) = the smallest camera-space z in
+ * [znear, zfar] at which the ray through the pixel centre (j + 0.5, i + 0.5)
+ * meets a triangle, 0 where it meets none.  Both facings count, edges are
+ * inclusive, degenerate triangles cover nothing, a triangle that crosses znear
+ * or z = 0 contributes its part inside the slab.  float32 in a fixed operation
+ * order without fused multiply-add; the winner per pixel is an
+ * integer minimum, so the map is the same bits for any face order and on every
+ * run.  stage_ms: clear, set-up and small triangles, unit scan, wave units,
+ * finish.
+ *
+ * gsr_mesh_view_votes: counts [V] int32 (device) = the number of the n_views
+ * views with 0 <= u <= W - 1, 0 <= v <= H - 1, z > 0 and (d <= 0 or z < d + eps),
+ * where z = z_cam + 1e-8, (u, v) = K p_cam / z and d is the bilinear sample of
+ * that view's depth map at (u, v) (integer coordinates are pixel indices, the
+ * border repeated, empty pixels blended in as 0).  The views are rendered one
+ * after another into one depth buffer on `stream`; nothing is read back
+ * between them.  stage_ms: the same stages summed over the views, then the
+ * vote.
+ *
+ * Both return GSR_ERR_ARGS unless 1 <= H, W <= 16384, fx, fy > 0,
+ * 0 < znear <= zfar and every camera number (and eps) is finite.
+ * Both call scratch_alloc once (4 bytes per pixel, 12 per triangle, the scan's
+ * temporary) and synchronise `stream` once, at the end: a face that names a
+ * vertex outside [0, V) is GSR_ERR_ARGS.  `counters` (host, optional, 4 words;
+ * measurement only, it selects slower counting kernels): atomics issued, pixel
+ * centres tested, triangles drawn by one lane, wave units.
+ */
+int gsr_mesh_depth(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long V, const float* vertices, long long F,
+                   const void* faces, int faces_int64, const float* w2c, int H, int W, float fx, float fy, float cx,
+                   float cy, float znear, float zfar, float* depth, unsigned long long* counters, float* stage_ms,
+                   void* stream);
+int gsr_mesh_view_votes(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long V, const float* vertices, long long F,
+                        const void* faces, int faces_int64, int n_views, const float* w2cs, int H, int W, float fx,
+                        float fy, float cx, float cy, float znear, float zfar, float eps, int* counts,
+                        unsigned long long* counters, float* stage_ms, void* stream);
+
+/*
  * Per-stage GPU timing (no reference equivalent; SURVEY §5 "tracing").  While
  * enabled, every kernel stage of the calls above is bracketed by two hipEvents
  * on the call's stream.  gsr_timing_collect() waits for the recorded events,
