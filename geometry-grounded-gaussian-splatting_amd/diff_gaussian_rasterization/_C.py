@@ -25,114 +25,13 @@ shared library must load, otherwise these functions raise.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("GSR_LIB") or os.path.join(_HERE, "libgsr.so")  # GSR_LIB: development A/B builds
-
-_ALLOC = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
-_CHUNK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int)  # gsr_chunk_fn
-_lib = None
-
-
-class AdamGroup(ctypes.Structure):
-    """gsr_adam_group (include/gsr.h)."""
-    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
-                ("exp_avg_sq", ctypes.c_void_p), ("n", ctypes.c_longlong), ("lr", ctypes.c_double)]
-
-
-# include/gsr.h ABI these bindings are written for (gsr_abi_version)
-ABI_VERSION = 20
-
-
-def _load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"libgsr.so not built ({LIB_PATH}); run `make -C geometry-grounded-gaussian-splatting_amd` "
-                           "or __graft_entry__.build()")
-    L = ctypes.CDLL(LIB_PATH)
-    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    L.gsr_abi_version.restype = i
-    if L.gsr_abi_version() != ABI_VERSION:  # the argtypes below are written for this ABI
-        raise RuntimeError(f"{LIB_PATH}: ABI {L.gsr_abi_version()}, expected {ABI_VERSION} (stale build? "
-                           "run `make -C geometry-grounded-gaussian-splatting_amd`)")
-    L.gsr_rasterize_forward.restype = i
-    L.gsr_rasterize_forward.argtypes = ([_ALLOC, vp] * 4 + [i] * 5 + [vp, i, i] + [vp] * 10 + [f] + [vp] * 3
-                                        + [f] * 3 + [i] + [vp] * 5 + [i, i, vp, ctypes.POINTER(i)])
-    L.gsr_rasterize_forward_ex.restype = i
-    L.gsr_rasterize_forward_ex.argtypes = L.gsr_rasterize_forward.argtypes + [_ALLOC, vp]
-    L.gsr_rasterize_backward.restype = i
-    L.gsr_rasterize_backward.argtypes = ([_ALLOC, vp] + [i] * 6 + [vp, i, i] + [vp] * 10 + [f] + [vp] * 3
-                                         + [f] * 3 + [vp] * 4 + [vp] * 4 + [vp] * 4 + [vp] * 11 + [i, i, vp])
-    L.gsr_rasterize_backward_ex.restype = i
-    L.gsr_rasterize_backward_ex.argtypes = L.gsr_rasterize_backward.argtypes[:-1] + [i, _CHUNK, vp, vp, vp]
-    L.gsr_rasterize_forward_ex2.restype = i
-    L.gsr_rasterize_forward_ex2.argtypes = L.gsr_rasterize_forward_ex.argtypes + [vp]
-    L.gsr_rasterize_backward_ex2.restype = i
-    L.gsr_rasterize_backward_ex2.argtypes = L.gsr_rasterize_backward_ex.argtypes + [vp, vp]
-    L.gsr_sample_depth_forward.restype = i
-    L.gsr_sample_depth_forward.argtypes = ([_ALLOC, vp] * 6 + [i] * 4 + [vp] * 4 + [f] + [vp] * 5 + [f] * 3 + [i]
-                                           + [vp, vp, i, vp] + [ctypes.POINTER(i)] * 3)
-    L.gsr_sample_depth_forward_ex.restype = i
-    L.gsr_sample_depth_forward_ex.argtypes = L.gsr_sample_depth_forward.argtypes + [_ALLOC, vp]
-    L.gsr_integrate_forward.restype = i
-    L.gsr_integrate_forward.argtypes = ([_ALLOC, vp] * 6 + [i] * 4 + [vp] * 4 + [f] + [vp] * 6 + [f] * 3 + [i]
-                                        + [vp, vp, i, vp, ctypes.POINTER(i)])
-    L.gsr_evaluate_sdf_forward.restype = i
-    L.gsr_evaluate_sdf_forward.argtypes = ([_ALLOC, vp] * 6 + [i] * 4 + [vp] * 4 + [f] + [vp] * 6 + [f] * 3 + [i]
-                                           + [vp, vp, vp, i, vp, ctypes.POINTER(i)])
-    L.gsr_sample_depth_backward.restype = i
-    L.gsr_sample_depth_backward.argtypes = ([_ALLOC, vp] + [i] * 7 + [vp] * 4 + [f] + [vp] * 5 + [f] * 3
-                                            + [vp] * 6 + [vp] * 2 + [vp] * 6 + [i, vp])
-    L.gsr_adam_step.restype = i
-    L.gsr_adam_step.argtypes = [i, ctypes.POINTER(AdamGroup), ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                ctypes.c_double, vp]
-    L.gsr_densify_stats.restype = i
-    L.gsr_densify_stats.argtypes = [i] + [vp] * 7
-    L.gsr_view_color_grads.restype = i
-    L.gsr_view_color_grads.argtypes = [i] * 6 + [vp] * 10
-    L.gsr_view_color_grads_chunked.restype = i
-    L.gsr_view_color_grads_chunked.argtypes = [i] * 7 + [vp] * 12
-    L.gsr_backward_chunk_size.restype = i
-    L.gsr_backward_chunk_size.argtypes = [i, i]
-    L.gsr_mark_visible.restype = i
-    L.gsr_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
-    L.gsr_set_option.argtypes = [i, i]
-    L.gsr_debug_binning.argtypes = [vp, vp, i, i, i, vp, vp, vp]
-    L.gsr_debug_image.argtypes = [vp, i, i, vp, vp]
-    L.gsr_debug_tile_stats.argtypes = [vp, i, i, vp, vp]
-    L.gsr_debug_sample_points.argtypes = [vp, i, vp, vp, vp]
-    L.gsr_debug_render_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i]
-    L.gsr_debug_depth_sort_tile_keys.restype = i
-    L.gsr_debug_depth_sort_tile_keys.argtypes = [i]
-    L.gsr_debug_depth_sort_bytes.restype = ctypes.c_longlong
-    L.gsr_debug_depth_sort_bytes.argtypes = [i]
-    L.gsr_debug_depth_sort.restype = i
-    L.gsr_debug_depth_sort.argtypes = [i, vp, vp, vp, vp, i, vp]
-    L.gsr_debug_list_constants.restype = i
-    L.gsr_debug_list_constants.argtypes = [ctypes.POINTER(i), i]
-    L.gsr_debug_scan_excl_bytes.restype = ctypes.c_longlong
-    L.gsr_debug_scan_excl_bytes.argtypes = [ctypes.c_longlong]
-    L.gsr_debug_scan_excl.restype = i
-    L.gsr_debug_scan_excl.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_uint, vp, ctypes.c_uint, vp, vp]
-    L.gsr_timing_enable.argtypes = [i]
-    L.gsr_timing_stage_mask.argtypes = [ctypes.c_uint]
-    L.gsr_timing_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i)]
-    L.gsr_stage_name.restype = ctypes.c_char_p
-    L.gsr_stage_name.argtypes = [i]
-    L.gsr_last_error.restype = ctypes.c_char_p
-    _lib = L
-    return L
-
-
-def loaded_library_path() -> str:
-    _load()
-    return LIB_PATH
-
+# (the binding itself is _abi; its names are re-exported here under the ones callers and tests know, and
+# this module's functions take _ScratchBlocks from these globals, where a test may replace it)
+from ._abi import _ALLOC, _CHUNK, ABI_VERSION, LIB_PATH, AdamGroup, Out, call, loaded_library_path  # noqa: F401
+from ._abi import ScratchBlocks as _ScratchBlocks, check as _check, load as _load, ptr as _ptr, stream as _stream
 
 NUM_STAGES = 14
 # debugging aid: keep the last backward's accumulator buffer (gsr_api.hip
@@ -253,7 +152,6 @@ def debug_depth_sort(keys, prepared: bool = True):
                            f"{keys.dim()}-D)")
     if not keys.is_contiguous():
         raise RuntimeError("gsr debug_depth_sort: `keys` must be contiguous")
-    L = _load()
     P = keys.numel()
     if P >= 2 ** 31:
         raise RuntimeError("gsr debug_depth_sort: at most 2^31 - 1 keys")
@@ -261,10 +159,9 @@ def debug_depth_sort(keys, prepared: bool = True):
     keys_sorted = torch.empty_like(keys)
     if P == 0:
         return order, keys_sorted
-    scratch = torch.empty(L.gsr_debug_depth_sort_bytes(P), dtype=torch.uint8, device=keys.device)
-    with torch.cuda.device(keys.device):
-        _check(L.gsr_debug_depth_sort(P, _ptr(keys), _ptr(keys_sorted), _ptr(order), _ptr(scratch),
-                                      int(bool(prepared)), _stream(keys.device)))
+    scratch = torch.empty(_load().gsr_debug_depth_sort_bytes(P), dtype=torch.uint8, device=keys.device)
+    call(keys.device, "gsr_debug_depth_sort", P, _ptr(keys), _ptr(keys_sorted), _ptr(order), _ptr(scratch),
+         int(bool(prepared)), _stream(keys.device))
     return order, keys_sorted
 
 
@@ -315,13 +212,10 @@ def debug_scan_excl(inp, out, cap: int, n: int = 0, n_dev=None, mul: int = 1) ->
     N = int(n) if n_dev is None else mul * (int(n_dev[0].item()) & 0xFFFFFFFF)  # (a test hook: one readback)
     if not 0 <= N <= cap or not 0 <= mul < 2 ** 32:
         raise RuntimeError(f"gsr debug_scan_excl: length {N} outside [0, cap = {cap}]")
-    L = _load()
     sums = torch.empty(debug_scan_excl_bytes(cap), dtype=torch.uint8, device=inp.device)
-    with torch.cuda.device(inp.device):
-        _check(L.gsr_debug_scan_excl(ctypes.c_void_p(inp.data_ptr()), ctypes.c_void_p(out.data_ptr()), cap,
-                                     0 if n_dev is not None else N,
-                                     None if n_dev is None else ctypes.c_void_p(n_dev.data_ptr()), mul, _ptr(sums),
-                                     _stream(inp.device)))
+    call(inp.device, "gsr_debug_scan_excl", ctypes.c_void_p(inp.data_ptr()), ctypes.c_void_p(out.data_ptr()), cap,
+         0 if n_dev is not None else N, None if n_dev is None else ctypes.c_void_p(n_dev.data_ptr()), mul, _ptr(sums),
+         _stream(inp.device))
 
 
 def set_option(opt: int, value: int) -> None:
@@ -354,51 +248,11 @@ def timing_collect() -> dict:
     return {L.gsr_stage_name(k).decode(): (ms[k], n[k]) for k in range(NUM_STAGES)}
 
 
-class _ByteBuffer:
+def _ByteBuffer(device, zero: bool = False):
     """A resizable torch.uint8 device tensor handed to the C ABI as a callback
-    (replaces resizeFunctional, DGR/rasterize_points.cu:27-37)."""
-
-    def __init__(self, device, zero: bool = False):
-        self.device = device
-        self.zero = zero
-        self.tensor = torch.empty(0, dtype=torch.uint8, device=device)
-
-        def _cb(_ctx, n):
-            try:
-                self.tensor = (torch.zeros if self.zero else torch.empty)(int(n), dtype=torch.uint8,
-                                                                           device=self.device)
-                return self.tensor.data_ptr() if n else self.tensor.data_ptr() or 1
-            except Exception:  # noqa: BLE001 - allocation failure is reported as NULL
-                return None
-
-        self.cb = _ALLOC(_cb)
-
-
-class _ScratchBlocks:
-    """Forward-only scratch for gsr_rasterize_forward_ex: every block the
-    callback hands out is kept until the forward returns, then dropped (the
-    caching allocator reuses it in stream order), so it is not saved for the
-    backward as the binning buffer is."""
-
-    def __init__(self, device):
-        self.device = device
-        self.blocks = []
-
-        def _cb(_ctx, n):
-            try:
-                t = torch.empty(max(int(n), 1), dtype=torch.uint8, device=self.device)
-                self.blocks.append(t)
-                return t.data_ptr()
-            except Exception:  # noqa: BLE001 - allocation failure is reported as NULL
-                return None
-
-        self.cb = _ALLOC(_cb)
-
-
-def _ptr(t):
-    if t is None or t.numel() == 0:
-        return None
-    return ctypes.c_void_p(t.data_ptr())
+    (replaces resizeFunctional, DGR/rasterize_points.cu:27-37): Out for uint8,
+    under the name callers outside this module know."""
+    return Out(device, torch.uint8, zero)
 
 
 def _dev_contig(t, name):
@@ -423,15 +277,6 @@ def _split_rest(sh, sh_rest, P):
     return _dev_contig(sh_rest, "sh_rest")
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check(rc):
-    if rc != 0:
-        raise RuntimeError("gsr: " + _lib.gsr_last_error().decode())
-
-
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, sh, sg_axis,
                         sg_sharpness, sg_color, sh_degree, sg_degree, scale_modifier, viewmatrix, projmatrix,
                         tan_fovx, tan_fovy, kernel_size, image_height, image_width, campos, prefiltered,
@@ -442,7 +287,6 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     them, without their concatenation (gsr_rasterize_forward_ex2)."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    L = _load()
     P = means3D.size(0)
     H, W = int(image_height), int(image_width)
     dev = means3D.device
@@ -465,21 +309,19 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     alpha = torch.empty(1, H, W, **fopt)
     normal = torch.empty(3, H, W, **fopt)
     radii = torch.empty(P, dtype=torch.int32, device=dev)
-    bufs = [_ByteBuffer(dev) for _ in range(4)]
+    bufs = [Out(dev, torch.uint8) for _ in range(4)]
     scratch = _ScratchBlocks(dev)
     K = ctypes.c_int(0)
-    with torch.cuda.device(dev):
-        rc = L.gsr_rasterize_forward_ex2(
-            bufs[0].cb, None, bufs[1].cb, None, bufs[2].cb, None, bufs[3].cb, None,
-            P, int(sh_degree), SHM, int(sg_degree), SGM, _ptr(args["background"]), W, H, _ptr(args["means3D"]),
-            _ptr(args["colors"]), _ptr(args["opacity"]), _ptr(args["scales"]), _ptr(args["rotations"]),
-            _ptr(args["cov3D_precomp"]), _ptr(args["sh"]), _ptr(args["sg_axis"]), _ptr(args["sg_sharpness"]),
-            _ptr(args["sg_color"]), float(scale_modifier), _ptr(args["viewmatrix"]), _ptr(args["projmatrix"]),
-            _ptr(args["campos"]), float(tan_fovx), float(tan_fovy), float(kernel_size), int(bool(prefiltered)),
-            _ptr(color), _ptr(mdepth), _ptr(alpha), _ptr(normal), _ptr(radii), int(bool(require_depth)),
-            int(bool(debug)), _stream(dev), ctypes.byref(K), scratch.cb, None, _ptr(rest))
+    call(dev, "gsr_rasterize_forward_ex2",
+         bufs[0].cb, None, bufs[1].cb, None, bufs[2].cb, None, bufs[3].cb, None,
+         P, int(sh_degree), SHM, int(sg_degree), SGM, _ptr(args["background"]), W, H, _ptr(args["means3D"]),
+         _ptr(args["colors"]), _ptr(args["opacity"]), _ptr(args["scales"]), _ptr(args["rotations"]),
+         _ptr(args["cov3D_precomp"]), _ptr(args["sh"]), _ptr(args["sg_axis"]), _ptr(args["sg_sharpness"]),
+         _ptr(args["sg_color"]), float(scale_modifier), _ptr(args["viewmatrix"]), _ptr(args["projmatrix"]),
+         _ptr(args["campos"]), float(tan_fovx), float(tan_fovy), float(kernel_size), int(bool(prefiltered)),
+         _ptr(color), _ptr(mdepth), _ptr(alpha), _ptr(normal), _ptr(radii), int(bool(require_depth)),
+         int(bool(debug)), _stream(dev), ctypes.byref(K), scratch.cb, None, _ptr(rest))
     del scratch
-    _check(rc)
     return (K.value, color, alpha, normal, mdepth, radii, bufs[0].tensor, bufs[1].tensor, bufs[2].tensor,
             bufs[3].tensor)
 
@@ -499,7 +341,6 @@ def rasterize_gaussians_backward(background, means3D, colors, opacity, scales, r
     rebuild before the gradients are used).  `sh_rest` (the split SH layout,
     see rasterize_gaussians): dsh is then [P, 1, 3] and a 12th gradient,
     dsh_rest [P, M-1, 3], is returned (gsr_rasterize_backward_ex2)."""
-    L = _load()
     P = means3D.size(0)
     img = dL_dout_color if dL_dout_color is not None else alphas  # (a None upstream gradient is zero)
     H, W = img.size(1), img.size(2)
@@ -524,7 +365,7 @@ def rasterize_gaussians_backward(background, means3D, colors, opacity, scales, r
             normalmap=normalmap, mdepth=mdepth, dL_dout_color=dL_dout_color, dL_dout_mdepth=dL_dout_mdepth,
             dL_dout_alpha=dL_dout_alpha, dL_dout_normal=dL_dout_normal).items()}
         radii = radii.contiguous()
-        scratch = _ByteBuffer(dev)
+        scratch = Out(dev, torch.uint8)
         grads = (outs["dmeans2D"], outs["dcolors"], outs["dopacity"], outs["dmeans3D"], outs["dcov3D"], outs["dsh"],
                  outs["dsg_axis"], outs["dsg_sharpness"], outs["dsg_color"], outs["dscales"], outs["drotations"])
         chunks, dc = 1, None
@@ -534,8 +375,8 @@ def rasterize_gaussians_backward(background, means3D, colors, opacity, scales, r
             dc = exchange.dc_rows(P, dev) if SHM else None
             cb = exchange.hook(grads)  # (errors held by the exchange, raised by settle below)
             hook = _CHUNK(lambda _ctx, b, e: cb(b, e))
-        with torch.cuda.device(dev):
-            rc = L.gsr_rasterize_backward_ex2(
+        with torch.cuda.device(dev):  # (not call(): the exchange settles on the status before it is raised)
+            rc = _load().gsr_rasterize_backward_ex2(
                 scratch.cb, None, P, int(sh_degree), SHM, int(sg_degree), SGM, int(R), _ptr(a["background"]), W, H,
                 _ptr(a["means3D"]), _ptr(a["colors"]), _ptr(a["opacity"]), _ptr(a["scales"]), _ptr(a["rotations"]),
                 _ptr(a["cov3D_precomp"]), _ptr(a["sh"]), _ptr(a["sg_axis"]), _ptr(a["sg_sharpness"]),
@@ -560,15 +401,14 @@ def rasterize_gaussians_backward(background, means3D, colors, opacity, scales, r
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):
-    L = _load()
     P = means3D.size(0)
     present = torch.zeros(P, dtype=torch.bool, device=means3D.device)
     if P != 0:
         m = _dev_contig(means3D, "means3D")
         v = _dev_contig(viewmatrix, "viewmatrix")
         p = _dev_contig(projmatrix, "projmatrix")
-        with torch.cuda.device(means3D.device):
-            _check(L.gsr_mark_visible(P, _ptr(m), _ptr(v), _ptr(p), _ptr(present), _stream(means3D.device)))
+        call(means3D.device, "gsr_mark_visible", P, _ptr(m), _ptr(v), _ptr(p), _ptr(present),
+             _stream(means3D.device))
     return present
 
 
@@ -582,7 +422,6 @@ def _point_query(fn, points3D, means3D, opacity, scales, rotations, scale_modifi
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if points3D.ndimension() != 2 or points3D.size(1) != 3:
         raise RuntimeError("points3D must have dimensions (num_points, 3)")
-    L = _load()
     PN, P = points3D.size(0), means3D.size(0)
     dev = means3D.device
     out0 = torch.zeros(PN, dtype=torch.float32, device=dev)
@@ -594,7 +433,7 @@ def _point_query(fn, points3D, means3D, opacity, scales, rotations, scale_modifi
             points3D=points3D, means3D=means3D, opacity=opacity, scales=scales, rotations=rotations,
             cov3D_precomp=cov3D_precomp, view2gaussian_precomp=view2gaussian_precomp, viewmatrix=viewmatrix,
             projmatrix=projmatrix, campos=campos).items()}
-        bufs = [_ByteBuffer(dev) for _ in range(6)]
+        bufs = [Out(dev, torch.uint8) for _ in range(6)]
         head = [bufs[0].cb, None, bufs[1].cb, None, bufs[2].cb, None, bufs[3].cb, None, bufs[4].cb, None,
                 bufs[5].cb, None, PN, P, int(image_width), int(image_height), _ptr(a["points3D"]),
                 _ptr(a["means3D"]), _ptr(a["opacity"]), _ptr(a["scales"]), float(scale_modifier),
@@ -602,10 +441,8 @@ def _point_query(fn, points3D, means3D, opacity, scales, rotations, scale_modifi
                 _ptr(a["viewmatrix"]), _ptr(a["projmatrix"]), _ptr(a["campos"]), float(tan_fovx), float(tan_fovy),
                 float(kernel_size), int(bool(prefiltered))]
         outs = [_ptr(out0)] if fn == "integrate" else [_ptr(out0), _ptr(out1)]
-        with torch.cuda.device(dev):
-            entry = L.gsr_integrate_forward if fn == "integrate" else L.gsr_evaluate_sdf_forward
-            rc = entry(*head, *outs, _ptr(inside), int(bool(debug)), _stream(dev), ctypes.byref(K))
-        _check(rc)
+        call(dev, "gsr_integrate_forward" if fn == "integrate" else "gsr_evaluate_sdf_forward", *head, *outs,
+             _ptr(inside), int(bool(debug)), _stream(dev), ctypes.byref(K))
     return K.value, out0, out1, inside
 
 
@@ -642,30 +479,27 @@ def sample_rasterized_depth(points3D, means3D, opacity, scales, rotations, scale
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if points3D.ndimension() < 1 or points3D.size(-1) != 3:
         raise RuntimeError("points3D must have shape (..., 3) with last dimension == 3")
-    L = _load()
     PN = points3D.numel() // 3
     P = means3D.size(0)
     H, W = int(image_height), int(image_width)
     dev = means3D.device
     output = torch.zeros_like(points3D)
     inside = torch.zeros(points3D.shape[:-1], dtype=torch.bool, device=points3D.device)
-    bufs = [_ByteBuffer(dev) for _ in range(6)]
+    bufs = [Out(dev, torch.uint8) for _ in range(6)]
     scratch = _ScratchBlocks(dev)
     K, RN, TN = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     if P != 0 and PN != 0:
         a = {k: _dev_contig(v, k) for k, v in dict(
             points3D=points3D, means3D=means3D, opacity=opacity, scales=scales, rotations=rotations,
             cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos).items()}
-        with torch.cuda.device(dev):
-            rc = L.gsr_sample_depth_forward_ex(
-                bufs[0].cb, None, bufs[1].cb, None, bufs[2].cb, None, bufs[3].cb, None, bufs[4].cb, None,
-                bufs[5].cb, None, PN, P, W, H, _ptr(a["points3D"]), _ptr(a["means3D"]), _ptr(a["opacity"]),
-                _ptr(a["scales"]), float(scale_modifier), _ptr(a["rotations"]), _ptr(a["cov3D_precomp"]),
-                _ptr(a["viewmatrix"]), _ptr(a["projmatrix"]), _ptr(a["campos"]), float(tan_fovx), float(tan_fovy),
-                float(kernel_size), int(bool(prefiltered)), _ptr(output), _ptr(inside), int(bool(debug)),
-                _stream(dev), ctypes.byref(K), ctypes.byref(RN), ctypes.byref(TN), scratch.cb, None)
+        call(dev, "gsr_sample_depth_forward_ex",
+             bufs[0].cb, None, bufs[1].cb, None, bufs[2].cb, None, bufs[3].cb, None, bufs[4].cb, None,
+             bufs[5].cb, None, PN, P, W, H, _ptr(a["points3D"]), _ptr(a["means3D"]), _ptr(a["opacity"]),
+             _ptr(a["scales"]), float(scale_modifier), _ptr(a["rotations"]), _ptr(a["cov3D_precomp"]),
+             _ptr(a["viewmatrix"]), _ptr(a["projmatrix"]), _ptr(a["campos"]), float(tan_fovx), float(tan_fovy),
+             float(kernel_size), int(bool(prefiltered)), _ptr(output), _ptr(inside), int(bool(debug)),
+             _stream(dev), ctypes.byref(K), ctypes.byref(RN), ctypes.byref(TN), scratch.cb, None)
         del scratch
-        _check(rc)
     res = (K.value, RN.value, TN.value, output, inside, *[b.tensor for b in bufs])
     if CAPTURE_SAMPLE:
         global last_sample
@@ -678,7 +512,6 @@ def sample_rasterized_depth_backward(points3D, means3D, opacity, scales, rotatio
                                      image_height, image_width, campos, geomBuffer, binningBuffer, pointBuffer,
                                      pointBinningBuffer, tileBuffer, duplicatedTileBuffer, R, RN, TN, prefiltered,
                                      debug):
-    L = _load()
     PN = points3D.numel() // 3
     P = means3D.size(0)
     dev = means3D.device
@@ -694,18 +527,16 @@ def sample_rasterized_depth_backward(points3D, means3D, opacity, scales, rotatio
         ins = inside.contiguous()
         if not ins.is_cuda or ins.dtype != torch.bool:
             raise RuntimeError("gsr: `inside` must be the forward's bool device tensor")
-        scratch = _ByteBuffer(dev)
-        with torch.cuda.device(dev):
-            rc = L.gsr_sample_depth_backward(
-                scratch.cb, None, PN, P, int(RN), int(R), int(TN), int(image_width), int(image_height),
-                _ptr(a["points3D"]), _ptr(a["means3D"]), _ptr(a["opacity"]), _ptr(a["scales"]), float(scale_modifier),
-                _ptr(a["rotations"]), _ptr(a["cov3D_precomp"]), _ptr(a["viewmatrix"]), _ptr(a["projmatrix"]),
-                _ptr(a["campos"]), float(tan_fovx), float(tan_fovy), float(kernel_size), _ptr(geomBuffer),
-                _ptr(binningBuffer), _ptr(pointBuffer), _ptr(pointBinningBuffer), _ptr(tileBuffer),
-                _ptr(duplicatedTileBuffer), _ptr(ins), _ptr(a["dL_doutput"]), _ptr(outs["dopacity"]),
-                _ptr(outs["dmeans3D"]), _ptr(outs["dcov3D"]), _ptr(outs["dscales"]), _ptr(outs["drotations"]),
-                _ptr(outs["dpoints3D"]), int(bool(debug)), _stream(dev))
-        _check(rc)
+        scratch = Out(dev, torch.uint8)
+        call(dev, "gsr_sample_depth_backward",
+             scratch.cb, None, PN, P, int(RN), int(R), int(TN), int(image_width), int(image_height),
+             _ptr(a["points3D"]), _ptr(a["means3D"]), _ptr(a["opacity"]), _ptr(a["scales"]), float(scale_modifier),
+             _ptr(a["rotations"]), _ptr(a["cov3D_precomp"]), _ptr(a["viewmatrix"]), _ptr(a["projmatrix"]),
+             _ptr(a["campos"]), float(tan_fovx), float(tan_fovy), float(kernel_size), _ptr(geomBuffer),
+             _ptr(binningBuffer), _ptr(pointBuffer), _ptr(pointBinningBuffer), _ptr(tileBuffer),
+             _ptr(duplicatedTileBuffer), _ptr(ins), _ptr(a["dL_doutput"]), _ptr(outs["dopacity"]),
+             _ptr(outs["dmeans3D"]), _ptr(outs["dcov3D"]), _ptr(outs["dscales"]), _ptr(outs["drotations"]),
+             _ptr(outs["dpoints3D"]), int(bool(debug)), _stream(dev))
     return (outs["dopacity"], outs["dmeans3D"], outs["dcov3D"], outs["dscales"], outs["drotations"],
             outs["dpoints3D"])
 
@@ -717,7 +548,6 @@ def adam_step(tensors, lrs, step: float, beta1: float, beta2: float, eps: float)
     """One Adam update (gsr_adam_step) of up to 16 (param, grad, exp_avg,
     exp_avg_sq) fp32 device tensors, contiguous, each with its learning rate,
     all at step count `step` (after increment)."""
-    L = _load()
     if not tensors:
         return
     arr = (AdamGroup * len(tensors))()
@@ -728,13 +558,11 @@ def adam_step(tensors, lrs, step: float, beta1: float, beta2: float, eps: float)
                 raise RuntimeError(f"gsr adam: `{name}` must be a contiguous fp32 HIP tensor shaped like its param")
         dev = p.device
         arr[k] = AdamGroup(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr))
-    with torch.cuda.device(dev):
-        _check(L.gsr_adam_step(len(tensors), arr, float(step), float(beta1), float(beta2), float(eps), _stream(dev)))
+    call(dev, "gsr_adam_step", len(tensors), arr, float(step), float(beta1), float(beta2), float(eps), _stream(dev))
 
 
 def densify_stats(viewspace_grad, radii, max_radii2D, accum, accum_abs, denom) -> None:
     """add_densification_stats + max_radii2D (gsr_densify_stats), in place."""
-    L = _load()
     P = radii.numel()
     for t, name in ((viewspace_grad, "viewspace_grad"), (max_radii2D, "max_radii2D"), (accum, "accum"),
                     (accum_abs, "accum_abs"), (denom, "denom")):
@@ -747,9 +575,8 @@ def densify_stats(viewspace_grad, radii, max_radii2D, accum, accum_abs, denom) -
         raise RuntimeError("gsr densify_stats: shape mismatch")
     dev = radii.device
     r = radii.contiguous()
-    with torch.cuda.device(dev):
-        _check(L.gsr_densify_stats(P, _ptr(viewspace_grad), _ptr(r), _ptr(max_radii2D), _ptr(accum), _ptr(accum_abs),
-                                   _ptr(denom), _stream(dev)))
+    call(dev, "gsr_densify_stats", P, _ptr(viewspace_grad), _ptr(r), _ptr(max_radii2D), _ptr(accum), _ptr(accum_abs),
+         _ptr(denom), _stream(dev))
 
 
 def view_color_grads_chunked(gathered, campos, n_views: int, chunk: int, means3D, sh_degree: int, dL_dsh,
@@ -760,7 +587,6 @@ def view_color_grads_chunked(gathered, campos, n_views: int, chunk: int, means3D
     ranges of `chunk` Gaussians, campos [n_views, 4].  With `dL_dsh_rest` (the
     split SH layout) dL_dsh is the DC rows [P, 1, 3] and dL_dsh_rest the rest
     [P, SHM - 1, 3]."""
-    L = _load()
     P = means3D.shape[0]
     SHM = dL_dsh.shape[1] if dL_dsh_rest is None else 1 + dL_dsh_rest.shape[1]
     SGM = dL_dsg_color.shape[1] if dL_dsg_color is not None and dL_dsg_color.numel() else 0
@@ -785,11 +611,9 @@ def view_color_grads_chunked(gathered, campos, n_views: int, chunk: int, means3D
                                f"of shape {shape}")
     dev = means3D.device
     p = lambda t: _ptr(t) if t is not None and t.numel() else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _check(L.gsr_view_color_grads_chunked(P, int(sh_degree), SHM, int(sg_degree), SGM, int(n_views), int(chunk),
-                                              _ptr(gathered), _ptr(campos), _ptr(means3D), p(sg_axis),
-                                              p(sg_sharpness), p(sg_color), _ptr(dL_dsh), p(dL_dsg_axis),
-                                              p(dL_dsg_sharpness), p(dL_dsg_color), p(dL_dsh_rest), _stream(dev)))
+    call(dev, "gsr_view_color_grads_chunked", P, int(sh_degree), SHM, int(sg_degree), SGM, int(n_views), int(chunk),
+         _ptr(gathered), _ptr(campos), _ptr(means3D), p(sg_axis), p(sg_sharpness), p(sg_color), _ptr(dL_dsh),
+         p(dL_dsg_axis), p(dL_dsg_sharpness), p(dL_dsg_color), p(dL_dsh_rest), _stream(dev))
 
 
 def view_color_grads(gathered, n_views: int, means3D, sh_degree: int, dL_dsh, sg_degree: int = 0, sg_axis=None,
@@ -798,7 +622,6 @@ def view_color_grads(gathered, n_views: int, means3D, sh_degree: int, dL_dsh, sg
     """gsr_view_color_grads (view_grads.hip): the SH / SG gradient rows of a
     view-parallel step summed over `n_views` views, from the gathered
     [n_views, P * 3 + 4] DC rows + camera centres; outputs written in place."""
-    L = _load()
     P = means3D.shape[0]
     SHM = dL_dsh.shape[1]
     SGM = dL_dsg_color.shape[1] if dL_dsg_color is not None and dL_dsg_color.numel() else 0
@@ -827,7 +650,6 @@ def view_color_grads(gathered, n_views: int, means3D, sh_degree: int, dL_dsh, sg
                            f"{SHM} SH rows and {SGM} SG lobes")
     dev = means3D.device
     p = lambda t: _ptr(t) if t is not None and t.numel() else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _check(L.gsr_view_color_grads(P, int(sh_degree), SHM, int(sg_degree), SGM, int(n_views), _ptr(gathered),
-                                      _ptr(means3D), p(sg_axis), p(sg_sharpness), p(sg_color), _ptr(dL_dsh),
-                                      p(dL_dsg_axis), p(dL_dsg_sharpness), p(dL_dsg_color), _stream(dev)))
+    call(dev, "gsr_view_color_grads", P, int(sh_degree), SHM, int(sg_degree), SGM, int(n_views), _ptr(gathered),
+         _ptr(means3D), p(sg_axis), p(sg_sharpness), p(sg_color), _ptr(dL_dsh), p(dL_dsg_axis), p(dL_dsg_sharpness),
+         p(dL_dsg_color), _stream(dev))

@@ -26,7 +26,7 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization._abi import DensifyParam, call, check, load, ptr, stream
 
 ROLE_COPY, ROLE_XYZ, ROLE_SCALING = 0, 1, 2
 TIME_APPLY = False  # measurement (tools/bench_densify.py): last_densify["apply_ms"], adds a synchronisation
@@ -37,42 +37,7 @@ PARAMS = (("xyz", "_xyz", ROLE_XYZ), ("f_dc", "_features_dc", ROLE_COPY), ("f_re
           ("sg_color", "_sg_color", ROLE_COPY))
 
 
-class DensifyParam(ctypes.Structure):
-    """gsr_densify_param (include/gsr.h)."""
-    _fields_ = [("param", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
-                ("param_out", ctypes.c_void_p), ("exp_avg_out", ctypes.c_void_p), ("exp_avg_sq_out", ctypes.c_void_p),
-                ("width", ctypes.c_int), ("role", ctypes.c_int)]
-
-
-def _lib():
-    L = _C._load()
-    if not getattr(L, "_densify_bound", False):
-        vp, i, ll, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-        L.gsr_densify_workspace_bytes.restype = ll
-        L.gsr_densify_workspace_bytes.argtypes = [ll]
-        L.gsr_densify_plan.restype = i
-        L.gsr_densify_plan.argtypes = [ll] + [vp] * 5 + [f, f, f, vp, ctypes.POINTER(ll), ctypes.POINTER(f), vp]
-        L.gsr_densify_apply.restype = i
-        L.gsr_densify_apply.argtypes = [ll, ctypes.POINTER(ll), vp, vp, i, vp, ll, vp, vp, i,
-                                        ctypes.POINTER(DensifyParam), vp]
-        L.gsr_quantile_workspace_bytes.restype = ll
-        L.gsr_quantile_workspace_bytes.argtypes = []
-        L.gsr_quantile.restype = i
-        L.gsr_quantile.argtypes = [ll, vp, vp, vp, vp, vp]
-        L.gsr_filter_3d.restype = i
-        L.gsr_filter_3d.argtypes = [ll, vp, i, vp, f, vp, vp, vp]
-        L.gsr_reset_opacity.restype = i
-        L.gsr_reset_opacity.argtypes = [ll] + [vp] * 7
-        L._densify_bound = True
-    return L
-
-
-def _rc(L, rc):
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-
-
-def _check(t, name, rows=None):
+def _f32(t, name, rows=None):
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
         raise RuntimeError(f"gsr densify: `{name}` must be a float32 HIP tensor")
     if not t.is_contiguous():
@@ -80,10 +45,6 @@ def _check(t, name, rows=None):
     if rows is not None and (t.dim() == 0 or t.shape[0] != rows):
         raise RuntimeError(f"gsr densify: `{name}` must have {rows} rows, got {tuple(t.shape)}")
     return t
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
 
 
 def _groups(optimizer):
@@ -124,30 +85,30 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size=
     torch.randn((C + 2 S, 3), generator=generator) after the plan's readback.
     `max_screen_size` is accepted and unused, as in the reference.  filter_3D
     is left as it was (stale): call compute_3D_filter afterwards."""
-    L = _lib()
     g = gaussians
     P = g._xyz.shape[0]
     dev = g._xyz.device
     srcs = {}
     for name, attr, role in PARAMS:
-        srcs[attr] = _check(getattr(g, attr).detach(), attr, P)
-    stats = [_check(getattr(g, a), a, P) for a in ("xyz_gradient_accum", "xyz_gradient_accum_abs", "denom")]
+        srcs[attr] = _f32(getattr(g, attr).detach(), attr, P)
+    stats = [_f32(getattr(g, a), a, P) for a in ("xyz_gradient_accum", "xyz_gradient_accum_abs", "denom")]
     if any(s.numel() != P for s in stats) or srcs["_opacity"].numel() != P or srcs["_scaling"].shape != (P, 3) \
             or srcs["_xyz"].shape != (P, 3) or srcs["_rotation"].shape != (P, 4):
         raise RuntimeError("gsr densify: statistics [P,1], _opacity [P,1], _scaling / _xyz [P,3], _rotation [P,4] expected")
+    L = load()
     nbytes = L.gsr_densify_workspace_bytes(P)
     if nbytes < 0:
         raise RuntimeError(f"gsr densify: {P} points are out of range")
     groups = _groups(g.optimizer)
-    with torch.cuda.device(dev):
-        stream = _C._stream(dev)
+    with torch.cuda.device(dev):  # (one guard over both calls: the apply's timing events record on this device)
+        strm = stream(dev)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         counts = (ctypes.c_longlong * 4)()
         Q = ctypes.c_float()
-        _rc(L, L.gsr_densify_plan(P, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(),
-                                  srcs["_scaling"].data_ptr(), srcs["_opacity"].data_ptr(), float(max_grad),
-                                  float(min_opacity), float(g.percent_dense * extent), ws.data_ptr(), counts,
-                                  ctypes.byref(Q), stream))
+        check(L.gsr_densify_plan(P, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(),
+                                 srcs["_scaling"].data_ptr(), srcs["_opacity"].data_ptr(), float(max_grad),
+                                 float(min_opacity), float(g.percent_dense * extent), ws.data_ptr(), counts,
+                                 ctypes.byref(Q), strm))
         C, S, pruned, N = (int(c) for c in counts)
         rows = C + 2 * S
         if noise is None:
@@ -156,7 +117,7 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size=
         elif not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (rows, 3):
             raise RuntimeError(f"gsr densify: noise must be [C + 2 S, 3] = [{rows}, 3] for this call, got "
                                f"{tuple(noise.shape) if isinstance(noise, torch.Tensor) else type(noise)}")
-        noise = _check(noise, "noise")
+        noise = _f32(noise, "noise")
         # Validate every moment before anything is replaced, then gather one parameter per launch and
         # hand it over at once: the source (and its moments) is released before the next output is
         # allocated, so the peak above the model's own bytes is one parameter with its two moments, not
@@ -165,7 +126,7 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size=
         for name, attr, role in PARAMS:
             st = g.optimizer.state.get(groups[name]["params"][0]) if name in groups else None
             if st is not None and "exp_avg" in st:
-                m, v = _check(st["exp_avg"], name + ".exp_avg", P), _check(st["exp_avg_sq"], name + ".exp_avg_sq", P)
+                m, v = _f32(st["exp_avg"], name + ".exp_avg", P), _f32(st["exp_avg_sq"], name + ".exp_avg_sq", P)
                 if m.shape != srcs[attr].shape or v.shape != srcs[attr].shape:
                     raise RuntimeError(f"gsr densify: the moments of `{name}` do not have the parameter's shape")
                 states[attr] = st
@@ -187,9 +148,9 @@ def densify_and_prune(gaussians, max_grad, min_opacity, extent, max_screen_size=
                 if TIME_APPLY:
                     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
                     ev[0].record()
-                _rc(L, L.gsr_densify_apply(P, counts, ws.data_ptr(), fmap.data_ptr(), int(first), _ptr(noise), rows,
-                                           rot_ptr if role == ROLE_XYZ else None,
-                                           scl_ptr if role == ROLE_XYZ else None, 1, ctypes.byref(desc), stream))
+                check(L.gsr_densify_apply(P, counts, ws.data_ptr(), fmap.data_ptr(), int(first), ptr(noise), rows,
+                                          rot_ptr if role == ROLE_XYZ else None,
+                                          scl_ptr if role == ROLE_XYZ else None, 1, ctypes.byref(desc), strm))
                 first = False
                 if TIME_APPLY:
                     ev[1].record()
@@ -222,17 +183,15 @@ def camera_records(cameras, device):
 @torch.no_grad()
 def filter_3D(xyz, cameras):
     """gaussian_model.py:225-262 for `xyz` [P,3]: the [P,1] 3D filter."""
-    L = _lib()
-    xyz = _check(xyz.detach(), "xyz")
+    xyz = _f32(xyz.detach(), "xyz")
     P = xyz.shape[0]
     if xyz.shape != (P, 3) or P == 0:
         raise RuntimeError("gsr densify: xyz [P,3] with P >= 1 expected")
     recs, focal = camera_records(cameras, xyz.device)
     out = torch.empty((P, 1), dtype=torch.float32, device=xyz.device)
     scratch = torch.empty(1, dtype=torch.int32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        _rc(L, L.gsr_filter_3d(P, xyz.data_ptr(), recs.shape[0], recs.data_ptr(), focal, out.data_ptr(),
-                               scratch.data_ptr(), _C._stream(xyz.device)))
+    call(xyz.device, "gsr_filter_3d", P, xyz.data_ptr(), recs.shape[0], recs.data_ptr(), focal, out.data_ptr(),
+         scratch.data_ptr(), stream(xyz.device))
     return out
 
 
@@ -252,20 +211,18 @@ def reset_3D_filter(gaussians):
 def reset_opacity(gaussians):
     """GaussianModel.reset_opacity: the filtered opacity capped at 0.01, as a new `_opacity`
     parameter of the "opacity" group with zeroed moments (replace_tensor_to_optimizer)."""
-    L = _lib()
     g = gaussians
     P = g._xyz.shape[0]
-    s, o = _check(g._scaling.detach(), "_scaling", P), _check(g._opacity.detach(), "_opacity", P)
-    f = _check(g.filter_3D, "filter_3D", P)
+    s, o = _f32(g._scaling.detach(), "_scaling", P), _f32(g._opacity.detach(), "_opacity", P)
+    f = _f32(g.filter_3D, "filter_3D", P)
     if s.shape != (P, 3) or o.numel() != P or f.numel() != P:
         raise RuntimeError("gsr densify: _scaling [P,3], _opacity [P,1], filter_3D [P,1] expected")
     group = _groups(g.optimizer).get("opacity")
     st = g.optimizer.state.get(group["params"][0]) if group is not None else None
     out = torch.empty_like(o)
     moments = (torch.empty_like(o), torch.empty_like(o)) if st is not None and "exp_avg" in st else None
-    with torch.cuda.device(o.device):
-        _rc(L, L.gsr_reset_opacity(P, _ptr(s), _ptr(o), _ptr(f), _ptr(out), _ptr(moments[0]) if moments else None,
-                                   _ptr(moments[1]) if moments else None, _C._stream(o.device)))
+    call(o.device, "gsr_reset_opacity", P, ptr(s), ptr(o), ptr(f), ptr(out), ptr(moments[0]) if moments else None,
+         ptr(moments[1]) if moments else None, stream(o.device))
     _replace(g, g.optimizer, group, "_opacity", out, moments)
 
 
@@ -273,14 +230,12 @@ def reset_opacity(gaussians):
 def quantile(values, q):
     """torch.quantile(values, q) (linear interpolation) for a flat float32 HIP tensor of
     non-negative values and a scalar q (float or 0-dim tensor), as a 0-dim device tensor."""
-    L = _lib()
-    v = _check(values, "values").reshape(-1)
+    v = _f32(values, "values").reshape(-1)
     if v.numel() == 0:
         raise RuntimeError("gsr densify: quantile of an empty tensor")
     qt = torch.as_tensor(q, dtype=torch.float32).to(v.device).reshape(1).contiguous()
     out = torch.empty((), dtype=torch.float32, device=v.device)
-    ws = torch.empty(L.gsr_quantile_workspace_bytes(), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        _rc(L, L.gsr_quantile(v.numel(), v.data_ptr(), qt.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                              _C._stream(v.device)))
+    ws = torch.empty(load().gsr_quantile_workspace_bytes(), dtype=torch.uint8, device=v.device)
+    call(v.device, "gsr_quantile", v.numel(), v.data_ptr(), qt.data_ptr(), out.data_ptr(), ws.data_ptr(),
+         stream(v.device))
     return out

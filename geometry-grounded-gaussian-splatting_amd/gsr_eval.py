@@ -18,8 +18,8 @@ import ctypes
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _G
-from gsr_mesh import _Out, _require
+from diff_gaussian_rasterization._abi import (Out, ScratchBlocks, call, ptr, record_stats, require, require_points,
+                                              stage_buffer, stream)
 
 SAMPLE_STAGES = ("count", "scan", "emit")
 THIN_STAGES = ("bounds", "sort", "rounds", "scan", "write")
@@ -29,36 +29,6 @@ NEAREST_STAGES = ("bounds", "ref_sort", "query_sort", "search")
 last_call_stats = None
 
 
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_pointeval_bound", False):
-        vp, i, ll, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double
-        fp = ctypes.POINTER(ctypes.c_float)
-        L.gsr_mesh_sample_points.restype = i
-        L.gsr_mesh_sample_points.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, ll, ll, vp, vp, i, d, ctypes.POINTER(ll),
-                                             fp, vp]
-        L.gsr_points_downsample.restype = i
-        L.gsr_points_downsample.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, ll, vp, d, ctypes.POINTER(ll),
-                                            ctypes.POINTER(ll), fp, vp]
-        L.gsr_points_nearest.restype = i
-        L.gsr_points_nearest.argtypes = [_G._ALLOC, vp, ll, vp, ll, vp, d, vp, fp, vp]
-        L._pointeval_bound = True
-    return L
-
-
-def _stats(stages, ms, scratch, **extra):
-    if last_call_stats is not None:
-        last_call_stats.clear()
-        last_call_stats.update({k: float(ms[i]) for i, k in enumerate(stages)},
-                               scratch_bytes=[int(b.numel()) for b in scratch.blocks], **extra)
-
-
-def _require_points(t, name, who):
-    _require(t, name, (torch.float64,), 2, who)
-    if t.size(1) != 3:
-        raise RuntimeError(f"{who}: `{name}` must have shape (N, 3) (got {tuple(t.shape)})")
-
-
 @torch.no_grad()
 def sample_mesh_points(vertices, faces, density=0.2):
     """eval.py:48-71 on the device: vertices [V,3] float32 / float64 (widened
@@ -66,8 +36,8 @@ def sample_mesh_points(vertices, faces, density=0.2):
     then per triangle with a non-zero area, in triangle order, the lattice
     points of sample_single_tri (i outer, j inner)."""
     who = "sample_mesh_points"
-    _require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
-    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
+    require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
+    require(faces, "faces", (torch.int32, torch.int64), 2, who)
     if vertices.size(1) != 3 or faces.size(1) != 3:
         raise RuntimeError(f"{who}: `vertices` and `faces` must have shapes (V, 3) and (F, 3) "
                            f"(got {tuple(vertices.shape)}, {tuple(faces.shape)})")
@@ -76,17 +46,12 @@ def sample_mesh_points(vertices, faces, density=0.2):
     dev = vertices.device
     vertices, faces = vertices.to(torch.float64).contiguous(), faces.contiguous()
     V, F = vertices.size(0), faces.size(0)
-    L = _lib()
-    out, scratch = _Out(dev, torch.float64), _G._ScratchBlocks(dev)
+    out, scratch = Out(dev, torch.float64), ScratchBlocks(dev)
     n = ctypes.c_longlong(0)
-    ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_mesh_sample_points(out.cb, None, scratch.cb, None, V, F, _G._ptr(vertices), _G._ptr(faces),
-                                      int(faces.dtype == torch.int64), float(density), ctypes.byref(n), ms,
-                                      _G._stream(dev))
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-    _stats(SAMPLE_STAGES, ms, scratch)
+    ms = stage_buffer(last_call_stats is not None)
+    call(dev, "gsr_mesh_sample_points", out.cb, None, scratch.cb, None, V, F, ptr(vertices), ptr(faces),
+         int(faces.dtype == torch.int64), float(density), ctypes.byref(n), ms, stream(dev))
+    record_stats(last_call_stats, SAMPLE_STAGES, ms, scratch)
     return out.tensor[:3 * n.value].view(-1, 3)
 
 
@@ -99,26 +64,22 @@ def downsample_points(points, radius, perm=None, generator=None):
     -> (kept_points [M,3] float64 in shuffled order, kept_index [M] int64 into
     the un-shuffled input)."""
     who = "downsample_points"
-    _require_points(points, "points", who)
+    require_points(points, "points", who)
     dev = points.device
     N = points.size(0)
     if perm is None:
         perm = torch.randperm(N, device=dev, generator=generator)
     else:
-        _require(perm, "perm", (torch.int64,), 1, who)
+        require(perm, "perm", (torch.int64,), 1, who)
         if perm.size(0) != N or perm.device != dev:
             raise RuntimeError(f"{who}: `perm` must have {N} entries on the device of `points`")
     shuffled = points[perm].contiguous()
-    L = _lib()
-    kept, scratch = _Out(dev, torch.int64), _G._ScratchBlocks(dev)
+    kept, scratch = Out(dev, torch.int64), ScratchBlocks(dev)
     M, rounds = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_points_downsample(kept.cb, None, scratch.cb, None, N, _G._ptr(shuffled), float(radius),
-                                     ctypes.byref(M), ctypes.byref(rounds), ms, _G._stream(dev))
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-    _stats(THIN_STAGES, ms, scratch, num_rounds=int(rounds.value))
+    ms = stage_buffer(last_call_stats is not None)
+    call(dev, "gsr_points_downsample", kept.cb, None, scratch.cb, None, N, ptr(shuffled), float(radius),
+         ctypes.byref(M), ctypes.byref(rounds), ms, stream(dev))
+    record_stats(last_call_stats, THIN_STAGES, ms, scratch, num_rounds=int(rounds.value))
     ranks = kept.tensor[:M.value]
     return shuffled[ranks], perm[ranks]
 
@@ -129,23 +90,19 @@ def nearest_distance(query, ref, max_dist):
     distance to the nearest ref point where that is < max_dist, +inf
     otherwise (eval.py:119-122, 132-134 discard everything >= max_dist)."""
     who = "nearest_distance"
-    _require_points(query, "query", who)
-    _require_points(ref, "ref", who)
+    require_points(query, "query", who)
+    require_points(ref, "ref", who)
     if query.device != ref.device:
         raise RuntimeError(f"{who}: `query` and `ref` must be on one device")
     dev = query.device
     query, ref = query.contiguous(), ref.contiguous()
     Q, R = query.size(0), ref.size(0)
     dist = torch.empty(Q, dtype=torch.float64, device=dev)
-    L = _lib()
-    scratch = _G._ScratchBlocks(dev)
-    ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_points_nearest(scratch.cb, None, Q, _G._ptr(query), R, _G._ptr(ref), float(max_dist),
-                                  _G._ptr(dist), ms, _G._stream(dev))
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-    _stats(NEAREST_STAGES, ms, scratch)
+    scratch = ScratchBlocks(dev)
+    ms = stage_buffer(last_call_stats is not None)
+    call(dev, "gsr_points_nearest", scratch.cb, None, Q, ptr(query), R, ptr(ref), float(max_dist), ptr(dist), ms,
+         stream(dev))
+    record_stats(last_call_stats, NEAREST_STAGES, ms, scratch)
     return dist
 
 
@@ -159,8 +116,8 @@ def dtu_chamfer(vertices, faces, stl_points, obs_mask, bb, res, plane, *, densit
     over an empty set is nan), n_sampled, n_down, n_in, n_in_obs, n_stl_above,
     dist_d2s [n_in_obs], dist_s2d [n_stl_above] (+inf where >= max_dist)."""
     who = "dtu_chamfer"
-    _require(stl_points, "stl_points", (torch.float32, torch.float64), 2, who)
-    _require(obs_mask, "obs_mask", (torch.bool, torch.uint8), 3, who)
+    require(stl_points, "stl_points", (torch.float32, torch.float64), 2, who)
+    require(obs_mask, "obs_mask", (torch.bool, torch.uint8), 3, who)
     if stl_points.size(1) != 3:
         raise RuntimeError(f"{who}: `stl_points` must have shape (S, 3) (got {tuple(stl_points.shape)})")
     dev = stl_points.device

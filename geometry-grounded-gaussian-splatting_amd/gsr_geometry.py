@@ -5,28 +5,9 @@ gsr_depth_to_normal_{forward,backward} (csrc/depth_normal.hip), differentiable
 in depth.  `view` needs image_width, image_height, Fx, Fy, Cx, Cy."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from diff_gaussian_rasterization import _C as _G
-
-
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_dn_bound", False):
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.gsr_depth_to_normal_forward.restype = i
-        L.gsr_depth_to_normal_forward.argtypes = [vp, i, i, f, f, f, f, vp, vp, vp]
-        L.gsr_depth_to_normal_backward.restype = i
-        L.gsr_depth_to_normal_backward.argtypes = [vp, i, i, f, f, f, f, vp, vp, vp]
-        L._dn_bound = True
-    return L
-
-
-def _check(L, rc):
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+from diff_gaussian_rasterization._abi import call, stream
 
 
 class _DepthToNormal(torch.autograd.Function):
@@ -35,12 +16,10 @@ class _DepthToNormal(torch.autograd.Function):
         if not depth.is_cuda or depth.dtype != torch.float32:
             raise RuntimeError("depth_to_normal: depth must be a float32 HIP tensor")
         d = depth.contiguous()
-        L = _lib()
         normal = torch.empty(3, H, W, dtype=torch.float32, device=d.device)
         valid = torch.empty(1, H, W, dtype=torch.bool, device=d.device)
-        with torch.cuda.device(d.device):
-            _check(L, L.gsr_depth_to_normal_forward(d.data_ptr(), H, W, Fx, Fy, Cx, Cy, normal.data_ptr(),
-                                                    valid.data_ptr(), _G._stream(d.device)))
+        call(d.device, "gsr_depth_to_normal_forward", d.data_ptr(), H, W, Fx, Fy, Cx, Cy, normal.data_ptr(),
+             valid.data_ptr(), stream(d.device))
         ctx.save_for_backward(d)
         ctx.cam = (H, W, Fx, Fy, Cx, Cy)
         ctx.mark_non_differentiable(valid)
@@ -53,12 +32,10 @@ class _DepthToNormal(torch.autograd.Function):
             return None, None, None, None, None, None, None
         (d,) = ctx.saved_tensors
         H, W, Fx, Fy, Cx, Cy = ctx.cam
-        L = _lib()
         g = g_normal.contiguous()
         dd = torch.empty_like(d)
-        with torch.cuda.device(d.device):
-            _check(L, L.gsr_depth_to_normal_backward(d.data_ptr(), H, W, Fx, Fy, Cx, Cy, g.data_ptr(), dd.data_ptr(),
-                                                     _G._stream(d.device)))
+        call(d.device, "gsr_depth_to_normal_backward", d.data_ptr(), H, W, Fx, Fy, Cx, Cy, g.data_ptr(), dd.data_ptr(),
+             stream(d.device))
         return dd, None, None, None, None, None, None
 
 

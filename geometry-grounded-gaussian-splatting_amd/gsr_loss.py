@@ -16,14 +16,13 @@ There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 import enum
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from diff_gaussian_rasterization import _C as _G
+from diff_gaussian_rasterization._abi import Out, call, dev32, ptr, stream
 
 
 class AppModel(enum.Enum):
@@ -53,59 +52,31 @@ def app_model_name(app_model) -> str:
     return name
 
 
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_photo_bound", False):
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.gsr_photo_loss_forward.restype = i
-        L.gsr_photo_loss_forward.argtypes = [_G._ALLOC, vp, i, i, i, i, f] + [vp] * 6 + [i] * 4 + [vp] * 5
-        L.gsr_photo_loss_backward.restype = i
-        L.gsr_photo_loss_backward.argtypes = [i, i, i, i, f] + [vp] * 6 + [i] * 4 + [vp] * 7
-        L._photo_bound = True
-    return L
-
-
-def _check(L, rc):
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-
-
-def _dev32(t, name):
-    if not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError(f"rgb_loss: `{name}` must be a float32 HIP tensor")
-    return t.contiguous()
-
-
 def _image(img, name):
     """[3,H,W] or [1,3,H,W], any strides (as fused_ssim._planes)."""
-    t = _dev32(img, name)
+    t = dev32(img, name, "rgb_loss")
     if t.dim() < 3 or t.shape[-3] != 3 or t.numel() != 3 * t.shape[-2] * t.shape[-1]:
         raise RuntimeError(f"rgb_loss: `{name}` must be [3, H, W]")
     return t, t.shape[-2], t.shape[-1]
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class _PhotoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, embedding, gain, gt, mask, bg, mode, crop, lam, with_ssim):
-        L = _lib()
         a, H, W = _image(image, "image")
         b, H2, W2 = _image(gt, "gt_image")
         if (H, W) != (H2, W2):
             raise RuntimeError("rgb_loss: image and gt_image must have the same shape")
-        m = None if mask is None else _dev32(mask, "mask")
+        m = None if mask is None else dev32(mask, "mask", "rgb_loss")
         if m is not None and m.numel() != H * W:
             raise RuntimeError("rgb_loss: `mask` must be [H, W]")
-        c = None if bg is None else _dev32(bg, "bg")
+        c = None if bg is None else dev32(bg, "bg", "rgb_loss")
         if c is not None and c.numel() != 3:
             raise RuntimeError("rgb_loss: `bg` must have 3 values")
-        e = None if embedding is None else _dev32(embedding, "embedding")
+        e = None if embedding is None else dev32(embedding, "embedding", "rgb_loss")
         if mode in _EMB_SHAPE and e is not None and tuple(e.shape) != _EMB_SHAPE[mode]:
             raise RuntimeError(f"rgb_loss: `embedding` must be {list(_EMB_SHAPE[mode])}")
-        g = None if gain is None else _dev32(gain, "gain")
+        g = None if gain is None else dev32(gain, "gain", "rgb_loss")
         top, left, Hc, Wc = crop
         if mode == 3 and g is not None and g.numel() != 3 * Hc * Wc:
             raise RuntimeError("rgb_loss: `gain` must be [3, crop_h, crop_w]")
@@ -114,11 +85,10 @@ class _PhotoLoss(torch.autograd.Function):
         out = torch.empty(3, dtype=torch.float32, device=dev)
         factors = torch.empty(9 * H * W, dtype=torch.float32, device=dev) if train and with_ssim else None
         sums = torch.empty(12, dtype=torch.float32, device=dev) if train and mode in _EMB_SHAPE else None
-        scratch = _G._ByteBuffer(dev)
-        with torch.cuda.device(dev):
-            _check(L, L.gsr_photo_loss_forward(scratch.cb, None, H, W, mode, int(with_ssim), lam, a.data_ptr(),
-                                               b.data_ptr(), _ptr(m), _ptr(c), _ptr(e), _ptr(g), top, left, Hc, Wc,
-                                               out.data_ptr(), None, _ptr(factors), _ptr(sums), _G._stream(dev)))
+        scratch = Out(dev, torch.uint8)
+        call(dev, "gsr_photo_loss_forward", scratch.cb, None, H, W, mode, int(with_ssim), lam, a.data_ptr(),
+             b.data_ptr(), ptr(m), ptr(c), ptr(e), ptr(g), top, left, Hc, Wc, out.data_ptr(), None, ptr(factors),
+             ptr(sums), stream(dev))
         ctx.meta = (H, W, mode, crop, lam, with_ssim, image.shape, train)
         ctx.save_for_backward(a, b, m, c, e, g, factors, sums)
         loss, l1, ssim = out[0], out[1], out[2]
@@ -127,7 +97,6 @@ class _PhotoLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _g1, _g2):
-        L = _lib()
         H, W, mode, crop, lam, with_ssim, shape, train = ctx.meta
         if not train:
             raise RuntimeError("rgb_loss: no gradient was asked for in the forward")
@@ -137,11 +106,9 @@ class _PhotoLoss(torch.autograd.Function):
         demb = torch.empty_like(e) if mode in _EMB_SHAPE else None
         dgain = torch.empty_like(g) if mode == 3 else None
         top, left, Hc, Wc = crop
-        with torch.cuda.device(a.device):
-            _check(L, L.gsr_photo_loss_backward(H, W, mode, int(with_ssim), lam, a.data_ptr(), b.data_ptr(), _ptr(m),
-                                                _ptr(c), _ptr(e), _ptr(g), top, left, Hc, Wc, _ptr(factors),
-                                                _ptr(sums), up.data_ptr(), dimg.data_ptr(), _ptr(demb), _ptr(dgain),
-                                                _G._stream(a.device)))
+        call(a.device, "gsr_photo_loss_backward", H, W, mode, int(with_ssim), lam, a.data_ptr(), b.data_ptr(), ptr(m),
+             ptr(c), ptr(e), ptr(g), top, left, Hc, Wc, ptr(factors), ptr(sums), up.data_ptr(), dimg.data_ptr(),
+             ptr(demb), ptr(dgain), stream(a.device))
         return dimg.reshape(shape), demb, dgain, None, None, None, None, None, None, None
 
 

@@ -26,7 +26,8 @@ import ctypes
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _G
+from diff_gaussian_rasterization._abi import (Out, ScratchBlocks, call, ptr, record_stats, require, require_mesh,
+                                              stage_buffer, stream)
 
 STAGES = ("flags", "count", "emit", "sort", "ranks", "edges", "faces")
 # measurement hook (tools/bench_tetmesh.py): when a dict, every call leaves its per-stage GPU
@@ -34,53 +35,15 @@ STAGES = ("flags", "count", "emit", "sort", "ranks", "edges", "faces")
 last_call_stats = None
 
 
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_tetmesh_bound", False):
-        vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-        L.gsr_marching_tetrahedra.restype = i
-        L.gsr_marching_tetrahedra.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, ll, ll, vp, i, vp, vp,
-                                              ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(ctypes.c_float),
-                                              vp]
-        L._tetmesh_bound = True
-    return L
-
-
-class _Int64Out:
-    """An int64 output of the C ABI, allocated by its callback once the size is known."""
-
-    def __init__(self, device):
-        self.tensor = torch.empty(0, dtype=torch.int64, device=device)
-
-        def _cb(_ctx, n):
-            try:
-                self.tensor = torch.empty(int(n) // 8, dtype=torch.int64, device=device)
-                return self.tensor.data_ptr() or 1
-            except Exception:  # noqa: BLE001 - allocation failure is reported as NULL
-                return None
-
-        self.cb = _G._ALLOC(_cb)
-
-
-def _require(t, name, dtypes, ndim, who="marching_tetrahedra"):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{who}: `{name}` must be a HIP device tensor")
-    if t.dtype not in dtypes:
-        raise RuntimeError(f"{who}: `{name}` must be {' or '.join(str(d) for d in dtypes)} "
-                           f"(got {t.dtype})")
-    if t.dim() != ndim:
-        raise RuntimeError(f"{who}: `{name}` must have {ndim} dimensions (got {tuple(t.shape)})")
-
-
 @torch.no_grad()
 def marching_tetrahedra_ids(tets, sdf, valid):
     """The unbatched kernel call: tets [T,4] int32 / int64, sdf [V] float32,
     valid [V] bool / uint8, all on one HIP device -> (edge_ids [E,2] int64,
     faces [F,3] int64).  Runs on the current stream."""
-    global last_call_stats
-    _require(tets, "tets", (torch.int32, torch.int64), 2)
-    _require(sdf, "sdf", (torch.float32,), 1)
-    _require(valid, "valids", (torch.bool, torch.uint8), 1)
+    who = "marching_tetrahedra"
+    require(tets, "tets", (torch.int32, torch.int64), 2, who)
+    require(sdf, "sdf", (torch.float32,), 1, who)
+    require(valid, "valids", (torch.bool, torch.uint8), 1, who)
     if tets.size(1) != 4:
         raise RuntimeError(f"marching_tetrahedra: `tets` must have shape (T, 4) (got {tuple(tets.shape)})")
     if valid.size(0) != sdf.size(0):
@@ -88,70 +51,18 @@ def marching_tetrahedra_ids(tets, sdf, valid):
     if sdf.device != tets.device or valid.device != tets.device:
         raise RuntimeError("marching_tetrahedra: inputs must be on one device")
     dev = tets.device
-    L = _lib()
     tets, sdf = tets.contiguous(), sdf.contiguous()
     valid = valid.contiguous().view(torch.uint8)
     T, V = tets.size(0), sdf.size(0)
-    edges, faces, scratch = _Int64Out(dev), _Int64Out(dev), _G._ScratchBlocks(dev)
+    edges, faces, scratch = Out(dev, torch.int64), Out(dev, torch.int64), ScratchBlocks(dev)
     E, F = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_marching_tetrahedra(edges.cb, None, faces.cb, None, scratch.cb, None, T, V, _G._ptr(tets),
-                                       int(tets.dtype == torch.int64), _G._ptr(sdf), _G._ptr(valid),
-                                       ctypes.byref(E), ctypes.byref(F), ms, _G._stream(dev))
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-    if last_call_stats is not None:
-        last_call_stats.clear()
-        last_call_stats.update({k: float(ms[i]) for i, k in enumerate(STAGES)},
-                               scratch_bytes=[int(b.numel()) for b in scratch.blocks])
+    ms = stage_buffer(last_call_stats is not None)
+    call(dev, "gsr_marching_tetrahedra", edges.cb, None, faces.cb, None, scratch.cb, None, T, V, ptr(tets),
+         int(tets.dtype == torch.int64), ptr(sdf), ptr(valid), ctypes.byref(E), ctypes.byref(F), ms, stream(dev))
+    record_stats(last_call_stats, STAGES, ms, scratch)
     if E.value == 0:
         return (torch.zeros(0, 2, dtype=torch.int64, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev))
     return edges.tensor[:2 * E.value].view(-1, 2), faces.tensor[:3 * F.value].view(-1, 3)
-
-
-class _Out:
-    """An output of the C ABI of any dtype, allocated by its callback once the size is known."""
-
-    def __init__(self, device, dtype):
-        self.tensor = torch.empty(0, dtype=dtype, device=device)
-        item = self.tensor.element_size()
-
-        def _cb(_ctx, n):
-            try:
-                self.tensor = torch.empty(int(n) // item, dtype=dtype, device=device)
-                return self.tensor.data_ptr() or 1
-            except Exception:  # noqa: BLE001 - allocation failure is reported as NULL
-                return None
-
-        self.cb = _G._ALLOC(_cb)
-
-
-def _clean_lib():
-    L = _lib()
-    if not getattr(L, "_meshclean_bound", False):
-        vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-        L.gsr_mesh_clusters.restype = i
-        L.gsr_mesh_clusters.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, ll, ll, vp, i, vp, vp,
-                                        ctypes.POINTER(ll), ctypes.POINTER(ctypes.c_float), vp]
-        L.gsr_mesh_filter.restype = i
-        L.gsr_mesh_filter.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, ll, ll, ll, vp, vp, i, vp, vp, vp,
-                                      ctypes.POINTER(ll), ctypes.POINTER(ll), vp]
-        L._meshclean_bound = True
-    return L
-
-
-def _require_mesh(vertices, faces, who, vertices_optional=False):
-    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
-    if faces.size(1) != 3:
-        raise RuntimeError(f"{who}: `faces` must have shape (F, 3) (got {tuple(faces.shape)})")
-    if vertices is None and vertices_optional:
-        return
-    _require(vertices, "vertices", (torch.float32,), 2, who)
-    if vertices.size(1) != 3:
-        raise RuntimeError(f"{who}: `vertices` must have shape (V, 3) (got {tuple(vertices.shape)})")
-    if vertices.device != faces.device:
-        raise RuntimeError(f"{who}: `vertices` and `faces` must be on one device")
 
 
 CLEAN_STAGES = ("keys", "sort", "union", "flatten", "ids", "counts", "area")
@@ -167,31 +78,22 @@ def cluster_connected_triangles(vertices, faces, num_vertices=None):
     clusters are numbered by their lowest triangle index.  Without vertices,
     `num_vertices` bounds the ids (default: 2^31, which costs the edge sort its
     widest keys).  One host readback (C).  Runs on the current stream."""
-    global last_call_stats
     who = "cluster_connected_triangles"
-    _require_mesh(vertices, faces, who, vertices_optional=True)
+    require_mesh(vertices, faces, who, vertices_optional=True)
     dev = faces.device
     F = faces.size(0)
     V = vertices.size(0) if vertices is not None else (1 << 31 if num_vertices is None else int(num_vertices))
     labels = torch.empty(F, dtype=torch.int64, device=dev)
-    counts, areas, scratch = _Out(dev, torch.int64), _Out(dev, torch.float64), _G._ScratchBlocks(dev)
+    counts, areas, scratch = Out(dev, torch.int64), Out(dev, torch.float64), ScratchBlocks(dev)
     if F == 0:
         return labels, counts.tensor, (areas.tensor if vertices is not None else None)
-    L = _clean_lib()
     faces = faces.contiguous()
     vertices = vertices.contiguous() if vertices is not None else None
     C = ctypes.c_longlong(0)
-    ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_mesh_clusters(counts.cb, None, areas.cb, None, scratch.cb, None, F, V, _G._ptr(faces),
-                                 int(faces.dtype == torch.int64), _G._ptr(vertices), _G._ptr(labels), ctypes.byref(C),
-                                 ms, _G._stream(dev))
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-    if last_call_stats is not None:
-        last_call_stats.clear()
-        last_call_stats.update({k: float(ms[i]) for i, k in enumerate(CLEAN_STAGES)},
-                               scratch_bytes=[int(b.numel()) for b in scratch.blocks])
+    ms = stage_buffer(last_call_stats is not None)
+    call(dev, "gsr_mesh_clusters", counts.cb, None, areas.cb, None, scratch.cb, None, F, V, ptr(faces),
+         int(faces.dtype == torch.int64), ptr(vertices), ptr(labels), ctypes.byref(C), ms, stream(dev))
+    record_stats(last_call_stats, CLEAN_STAGES, ms, scratch)
     return labels, counts.tensor[:C.value], (areas.tensor[:C.value] if vertices is not None else None)
 
 
@@ -206,7 +108,7 @@ def post_process_mesh(vertices, faces, cluster_to_keep=1, min_triangles=50):
     [F',3] int64), order and winding kept.  The threshold never leaves the
     device; the host reads three sizes (C, then V' and F' together)."""
     who = "post_process_mesh"
-    _require_mesh(vertices, faces, who)
+    require_mesh(vertices, faces, who)
     if isinstance(cluster_to_keep, bool) or not isinstance(cluster_to_keep, int) or cluster_to_keep < 1:
         raise ValueError(f"{who}: `cluster_to_keep` must be an integer >= 1 (got {cluster_to_keep!r})")
     dev = faces.device
@@ -219,15 +121,11 @@ def post_process_mesh(vertices, faces, cluster_to_keep=1, min_triangles=50):
     if cluster_to_keep > C:
         raise ValueError(f"{who}: `cluster_to_keep` = {cluster_to_keep} but the mesh has {C} clusters")
     n_min = torch.sort(counts).values[C - cluster_to_keep].clamp(min=int(min_triangles)).reshape(1).contiguous()
-    L = _clean_lib()
-    vout, fout, scratch = _Out(dev, torch.float32), _Out(dev, torch.int64), _G._ScratchBlocks(dev)
+    vout, fout, scratch = Out(dev, torch.float32), Out(dev, torch.int64), ScratchBlocks(dev)
     Vn, Fn = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    with torch.cuda.device(dev):
-        rc = L.gsr_mesh_filter(vout.cb, None, fout.cb, None, scratch.cb, None, F, V, C, _G._ptr(vertices),
-                               _G._ptr(faces), int(faces.dtype == torch.int64), _G._ptr(labels), _G._ptr(counts),
-                               _G._ptr(n_min), ctypes.byref(Vn), ctypes.byref(Fn), _G._stream(dev))
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+    call(dev, "gsr_mesh_filter", vout.cb, None, fout.cb, None, scratch.cb, None, F, V, C, ptr(vertices), ptr(faces),
+         int(faces.dtype == torch.int64), ptr(labels), ptr(counts), ptr(n_min), ctypes.byref(Vn), ctypes.byref(Fn),
+         stream(dev))
     return vout.tensor[:3 * Vn.value].view(-1, 3), fout.tensor[:3 * Fn.value].view(-1, 3)
 
 

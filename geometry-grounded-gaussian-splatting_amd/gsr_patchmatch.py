@@ -14,42 +14,15 @@ CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from diff_gaussian_rasterization import _C as _G
+from diff_gaussian_rasterization._abi import Out, call, dev32, stream
 from gaussian_renderer import sample_depth
 
 PIXEL_NOISE_TH = 1.0  # arguments/__init__.py multi_view_pixel_noise_th
 
 
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_pm_bound", False):
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.gsr_patchmatch_lift.restype = i
-        L.gsr_patchmatch_lift.argtypes = [i, i, f, f, f, f, vp, vp, vp, vp, vp]
-        L.gsr_patchmatch_lift_backward.restype = i
-        L.gsr_patchmatch_lift_backward.argtypes = [i, i, f, f, f, f, vp, vp, vp, vp]
-        common = [i, i] + [vp] * 6 + [f] * 5 + [vp] * 4 + [f] * 8 + [i, i] + [vp] * 4
-        L.gsr_patchmatch_terms_forward.restype = i
-        L.gsr_patchmatch_terms_forward.argtypes = [_G._ALLOC, vp] + common + [vp, vp]
-        L.gsr_patchmatch_terms_backward.restype = i
-        L.gsr_patchmatch_terms_backward.argtypes = common + [vp] * 6
-        L._pm_bound = True
-    return L
-
-
-def _check(L, rc):
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-
-
-def _f32(t, name):
-    if not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError(f"gsr patchmatch: `{name}` must be a float32 HIP tensor")
-    return t.contiguous()
+_WHO = "gsr patchmatch"
 
 
 class _Lift(torch.autograd.Function):
@@ -57,27 +30,23 @@ class _Lift(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, md, T, M, intr):
-        L = _lib()
         H, W = md.shape[-2:]
-        md_c, T_c, M_c = _f32(md, "median_depth"), _f32(T, "T"), _f32(M, "M")
+        md_c, T_c, M_c = dev32(md, "median_depth", _WHO), dev32(T, "T", _WHO), dev32(M, "M", _WHO)
         pts = torch.empty(H, W, 3, dtype=torch.float32, device=md.device)
-        with torch.cuda.device(md.device):
-            _check(L, L.gsr_patchmatch_lift(H, W, *intr, T_c.data_ptr(), M_c.data_ptr(), md_c.data_ptr(),
-                                            pts.data_ptr(), _G._stream(md.device)))
+        call(md.device, "gsr_patchmatch_lift", H, W, *intr, T_c.data_ptr(), M_c.data_ptr(), md_c.data_ptr(),
+             pts.data_ptr(), stream(md.device))
         ctx.save_for_backward(M_c)
         ctx.meta = (H, W, intr, md.shape)
         return pts
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib()
         (M_c,) = ctx.saved_tensors
         H, W, intr, shape = ctx.meta
         g = g.contiguous()
         dmd = torch.empty(shape, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _check(L, L.gsr_patchmatch_lift_backward(H, W, *intr, M_c.data_ptr(), g.data_ptr(), dmd.data_ptr(),
-                                                     _G._stream(g.device)))
+        call(g.device, "gsr_patchmatch_lift_backward", H, W, *intr, M_c.data_ptr(), g.data_ptr(), dmd.data_ptr(),
+             stream(g.device))
         return dmd, None, None, None
 
 
@@ -86,10 +55,9 @@ class _Terms(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, md, normal, pin, inside, consts):
-        L = _lib()
         H, W = md.shape[-2:]
         dev = md.device
-        md_c, n_c, p_c = _f32(md, "median_depth"), _f32(normal, "normal"), _f32(pin, "points")
+        md_c, n_c, p_c = dev32(md, "median_depth", _WHO), dev32(normal, "normal", _WHO), dev32(pin, "points", _WHO)
         ins = inside.contiguous()
         if (ins.dtype not in (torch.bool, torch.uint8) or ins.numel() != H * W or p_c.numel() != 3 * H * W
                 or n_c.numel() != 3 * H * W):
@@ -100,11 +68,10 @@ class _Terms(torch.autograd.Function):
         gd = torch.empty(H * W, dtype=torch.float32, device=dev)
         gn = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
         out = torch.empty(4, dtype=torch.float32, device=dev)
-        scratch = _G._ByteBuffer(dev)
+        scratch = Out(dev, torch.uint8)
         args = (H, W, md_c.data_ptr(), n_c.data_ptr(), p_c.data_ptr(), ins.data_ptr()) + consts.ptrs() + (
             w.data_ptr(), flags.data_ptr(), gd.data_ptr(), gn.data_ptr())
-        with torch.cuda.device(dev):
-            _check(L, L.gsr_patchmatch_terms_forward(scratch.cb, None, *args, out.data_ptr(), _G._stream(dev)))
+        call(dev, "gsr_patchmatch_terms_forward", scratch.cb, None, *args, out.data_ptr(), stream(dev))
         ctx.save_for_backward(md_c, n_c, p_c, ins, w, flags, gd, gn, out)
         ctx.consts = consts
         ctx.shapes = (md.shape, normal.shape, pin.shape)
@@ -113,7 +80,6 @@ class _Terms(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_geo, g_ncc):
-        L = _lib()
         md_c, n_c, p_c, ins, w, flags, gd, gn, out = ctx.saved_tensors
         H, W = md_c.shape[-2:]
         dev = md_c.device
@@ -123,9 +89,8 @@ class _Terms(torch.autograd.Function):
         dnormal = torch.empty(ctx.shapes[1], dtype=torch.float32, device=dev)
         args = (H, W, md_c.data_ptr(), n_c.data_ptr(), p_c.data_ptr(), ins.data_ptr()) + ctx.consts.ptrs() + (
             w.data_ptr(), flags.data_ptr(), gd.data_ptr(), gn.data_ptr())
-        with torch.cuda.device(dev):
-            _check(L, L.gsr_patchmatch_terms_backward(*args, out.data_ptr(), g.data_ptr(), dpin.data_ptr(),
-                                                      dmd.data_ptr(), dnormal.data_ptr(), _G._stream(dev)))
+        call(dev, "gsr_patchmatch_terms_backward", *args, out.data_ptr(), g.data_ptr(), dpin.data_ptr(),
+             dmd.data_ptr(), dnormal.data_ptr(), stream(dev))
         return dmd, dnormal, dpin, None, None
 
 
@@ -140,8 +105,8 @@ class _Consts:
             r_rel = wn[:3, :3].transpose(-1, -2) @ wv[:3, :3]  # :232-235
             self.t_rel = (-r_rel @ wv[3, :3] + wn[3, :3]).contiguous()
             self.R_ncc = r_rel.T.contiguous()  # passed as warp_patch_ncc's R (:239)
-        self.gray_r = _f32(view.gray_image.squeeze(), "view gray image")
-        self.gray_n = _f32(nearest.gray_image.squeeze(), "nearest gray image")
+        self.gray_r = dev32(view.gray_image.squeeze(), "view gray image", _WHO)
+        self.gray_n = dev32(nearest.gray_image.squeeze(), "nearest gray image", _WHO)
         self.view, self.nearest = view, nearest
 
     def ptrs(self):

@@ -33,9 +33,8 @@ import math
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _G
-from gsr_eval import _require_points
-from gsr_mesh import _Out, _require
+from diff_gaussian_rasterization._abi import (Out, PointIndex as _PointIndex, ScratchBlocks, call, f32ptr, f64ptr, load,
+                                              ptr, require, require_points, stage_buffer, stage_stats, stream)
 
 SCENES_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003,
               "Meetingroom": 0.01, "Truck": 0.005}
@@ -53,65 +52,12 @@ _AXIS = {"X": 0, "Y": 1, "Z": 2}
 measure_stages = False
 
 
-class _PointIndex(ctypes.Structure):  # gsr_point_index
-    _fields_ = [("R", ctypes.c_longlong), ("buffer", ctypes.c_void_p), ("bounds_min", ctypes.c_double * 3),
-                ("bounds_max", ctypes.c_double * 3), ("cell_size", ctypes.c_double), ("cells", ctypes.c_longlong * 3),
-                ("key_bits", ctypes.c_int * 3)]
-
-
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_tnteval_bound", False):
-        vp, i, ll, d, A = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, _G._ALLOC
-        fp, dp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
-        L.gsr_points_crop_polygon.restype = i
-        L.gsr_points_crop_polygon.argtypes = [A, vp, A, vp, A, vp, ll, vp, dp, i, d, d, i, dp, ctypes.POINTER(ll), fp,
-                                              vp]
-        L.gsr_points_voxel_mean.restype = i
-        L.gsr_points_voxel_mean.argtypes = [A, vp, A, vp, A, vp, A, vp, ll, vp, d, ctypes.POINTER(ll), fp, vp]
-        L.gsr_points_index_bytes.restype = ctypes.c_size_t
-        L.gsr_points_index_bytes.argtypes = [ll]
-        L.gsr_points_index_build.restype = i
-        L.gsr_points_index_build.argtypes = [A, vp, ll, vp, vp, ctypes.c_size_t, ctypes.POINTER(_PointIndex), fp, vp]
-        L.gsr_points_index_query.restype = i
-        L.gsr_points_index_query.argtypes = [A, vp, ctypes.POINTER(_PointIndex), ll, vp, d, vp, vp, fp, vp]
-        L.gsr_icp_accumulate.restype = i
-        L.gsr_icp_accumulate.argtypes = [A, vp, ll, vp, ll, vp, vp, i, dp, dp, fp, vp]
-        L.gsr_points_transform.restype = i
-        L.gsr_points_transform.argtypes = [ll, vp, dp, fp, vp]
-        f, up = ctypes.c_float, ctypes.POINTER(ctypes.c_ulonglong)
-        L.gsr_mesh_depth.restype = i
-        L.gsr_mesh_depth.argtypes = [A, vp, ll, vp, ll, vp, i, fp, i, i, f, f, f, f, f, f, vp, up, fp, vp]
-        L.gsr_mesh_view_votes.restype = i
-        L.gsr_mesh_view_votes.argtypes = [A, vp, ll, vp, ll, vp, i, i, fp, i, i, f, f, f, f, f, f, f, vp, up, fp, vp]
-        L._tnteval_bound = True
-    return L
-
-
-def _ms():
-    return (ctypes.c_float * 8)() if measure_stages else None
-
-
-def _stats(stages, ms, scratch=None, **extra):
-    return dict(stage_ms=None if ms is None else {k: float(ms[i]) for i, k in enumerate(stages)},
-                scratch_bytes=sum(int(b.numel()) for b in scratch.blocks) if scratch is not None else 0, **extra)
-
-
-def _check(L, rc):
-    if rc != 0:
-        raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-
-
 def _mat4(T, who):
     T = np.ascontiguousarray(np.asarray(T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T,
                                         dtype=np.float64))
     if T.shape != (4, 4):
         raise RuntimeError(f"{who}: a transform must have shape (4, 4) (got {T.shape})")
     return T
-
-
-def _dptr(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 # ---- readers -----------------------------------------------------------------------------------------------------
@@ -153,21 +99,17 @@ def crop_points(points, crop, transform=None):
     """open3d's SelectionPolygonVolume.crop_point_cloud after an optional 4x4: points [N,3] float64 ->
     (kept_index [K] int64 ascending, kept transformed points [K,3] float64, stats)."""
     who = "crop_points"
-    _require_points(points, "points", who)
+    require_points(points, "points", who)
     dev = points.device
     points = points.contiguous()
     poly = np.ascontiguousarray(np.asarray(crop["bounding_polygon"], dtype=np.float64).reshape(-1, 3))
     T = None if transform is None else _mat4(transform, who)
-    L = _lib()
-    kept, out, scratch = _Out(dev, torch.int64), _Out(dev, torch.float64), _G._ScratchBlocks(dev)
-    K, ms = ctypes.c_longlong(0), _ms()
-    with torch.cuda.device(dev):
-        rc = L.gsr_points_crop_polygon(kept.cb, None, out.cb, None, scratch.cb, None, points.size(0), _G._ptr(points),
-                                       None if T is None else _dptr(T), _AXIS[crop["orthogonal_axis"]],
-                                       float(crop["axis_min"]), float(crop["axis_max"]), poly.shape[0], _dptr(poly),
-                                       ctypes.byref(K), ms, _G._stream(dev))
-    _check(L, rc)
-    return kept.tensor[:K.value], out.tensor[:3 * K.value].view(-1, 3), _stats(CROP_STAGES, ms, scratch)
+    kept, out, scratch = Out(dev, torch.int64), Out(dev, torch.float64), ScratchBlocks(dev)
+    K, ms = ctypes.c_longlong(0), stage_buffer(measure_stages)
+    call(dev, "gsr_points_crop_polygon", kept.cb, None, out.cb, None, scratch.cb, None, points.size(0), ptr(points),
+         None if T is None else f64ptr(T), _AXIS[crop["orthogonal_axis"]], float(crop["axis_min"]),
+         float(crop["axis_max"]), poly.shape[0], f64ptr(poly), ctypes.byref(K), ms, stream(dev))
+    return kept.tensor[:K.value], out.tensor[:3 * K.value].view(-1, 3), stage_stats(CROP_STAGES, ms, scratch)
 
 
 @torch.no_grad()
@@ -176,18 +118,15 @@ def voxel_down_sample(points, voxel_size, return_cells=False):
     voxel, ascending in the voxel's (cx, cy, cz); stats) or, with return_cells, (means, counts [C] int64, cells
     [C,3] int64, stats)."""
     who = "voxel_down_sample"
-    _require_points(points, "points", who)
+    require_points(points, "points", who)
     dev = points.device
     points = points.contiguous()
-    L = _lib()
-    means, counts, cells = _Out(dev, torch.float64), _Out(dev, torch.int64), _Out(dev, torch.int64)
-    scratch = _G._ScratchBlocks(dev)
-    C, ms = ctypes.c_longlong(0), _ms()
-    with torch.cuda.device(dev):
-        rc = L.gsr_points_voxel_mean(means.cb, None, counts.cb, None, cells.cb, None, scratch.cb, None, points.size(0),
-                                     _G._ptr(points), float(voxel_size), ctypes.byref(C), ms, _G._stream(dev))
-    _check(L, rc)
-    st = _stats(VOXEL_STAGES, ms, scratch)
+    means, counts, cells = Out(dev, torch.float64), Out(dev, torch.int64), Out(dev, torch.int64)
+    scratch = ScratchBlocks(dev)
+    C, ms = ctypes.c_longlong(0), stage_buffer(measure_stages)
+    call(dev, "gsr_points_voxel_mean", means.cb, None, counts.cb, None, cells.cb, None, scratch.cb, None,
+         points.size(0), ptr(points), float(voxel_size), ctypes.byref(C), ms, stream(dev))
+    st = stage_stats(VOXEL_STAGES, ms, scratch)
     m = means.tensor[:3 * C.value].view(-1, 3)
     if return_cells:
         return m, counts.tensor[:C.value], cells.tensor[:3 * C.value].view(-1, 3), st
@@ -212,18 +151,15 @@ class NearestIndex:
     @torch.no_grad()
     def build(cls, ref):
         who = "NearestIndex.build"
-        _require_points(ref, "ref", who)
+        require_points(ref, "ref", who)
         dev = ref.device
         ref = ref.contiguous()
-        L = _lib()
         R = ref.size(0)
-        buffer = torch.empty(int(L.gsr_points_index_bytes(R)), dtype=torch.uint8, device=dev)
-        desc, scratch, ms = _PointIndex(), _G._ScratchBlocks(dev), _ms()
-        with torch.cuda.device(dev):
-            rc = L.gsr_points_index_build(scratch.cb, None, R, _G._ptr(ref), _G._ptr(buffer), buffer.numel(),
-                                          ctypes.byref(desc), ms, _G._stream(dev))
-        _check(L, rc)
-        return cls(ref, buffer, desc, _stats(BUILD_STAGES, ms, scratch, index_bytes=int(buffer.numel())))
+        buffer = torch.empty(int(load().gsr_points_index_bytes(R)), dtype=torch.uint8, device=dev)
+        desc, scratch, ms = _PointIndex(), ScratchBlocks(dev), stage_buffer(measure_stages)
+        call(dev, "gsr_points_index_build", scratch.cb, None, R, ptr(ref), ptr(buffer), buffer.numel(),
+             ctypes.byref(desc), ms, stream(dev))
+        return cls(ref, buffer, desc, stage_stats(BUILD_STAGES, ms, scratch, index_bytes=int(buffer.numel())))
 
     @torch.no_grad()
     def query(self, query, max_dist):
@@ -231,7 +167,7 @@ class NearestIndex:
         in `ref` of the nearest point with distance < max_dist (the lowest position among equally near ones),
         (+inf, -1) beyond."""
         who = "NearestIndex.query"
-        _require_points(query, "query", who)
+        require_points(query, "query", who)
         dev = query.device
         if dev != self.ref.device:
             raise RuntimeError(f"{who}: `query` must be on the device of the index")
@@ -239,13 +175,10 @@ class NearestIndex:
         Q = query.size(0)
         dist = torch.empty(Q, dtype=torch.float64, device=dev)
         index = torch.empty(Q, dtype=torch.int64, device=dev)
-        L = _lib()
-        scratch, ms = _G._ScratchBlocks(dev), _ms()
-        with torch.cuda.device(dev):
-            rc = L.gsr_points_index_query(scratch.cb, None, ctypes.byref(self.desc), Q, _G._ptr(query),
-                                          float(max_dist), _G._ptr(dist), _G._ptr(index), ms, _G._stream(dev))
-        _check(L, rc)
-        return dist, index, _stats(QUERY_STAGES, ms, scratch)
+        scratch, ms = ScratchBlocks(dev), stage_buffer(measure_stages)
+        call(dev, "gsr_points_index_query", scratch.cb, None, ctypes.byref(self.desc), Q, ptr(query),
+             float(max_dist), ptr(dist), ptr(index), ms, stream(dev))
+        return dist, index, stage_stats(QUERY_STAGES, ms, scratch)
 
 
 @torch.no_grad()
@@ -254,39 +187,32 @@ def icp_accumulate(source, ref, index, means=None):
     pass 1 -> [8] float64 numpy (n, sum d^2, sum s, sum t); with means [6] (m_s, m_t) pass 2 -> [10]
     (sum (s - m_s)(t - m_t)^T row-major, sum |s - m_s|^2).  -> (sums, stats)."""
     who = "icp_accumulate"
-    _require_points(source, "source", who)
-    _require_points(ref, "ref", who)
-    _require(index, "index", (torch.int64,), 1, who)
+    require_points(source, "source", who)
+    require_points(ref, "ref", who)
+    require(index, "index", (torch.int64,), 1, who)
     if index.size(0) != source.size(0) or ref.device != source.device or index.device != source.device:
         raise RuntimeError(f"{who}: `index` must have one entry per source point, all on one device")
     dev = source.device
     source, ref, index = source.contiguous(), ref.contiguous(), index.contiguous()
     sums = np.zeros(8 if means is None else 10, dtype=np.float64)
     m = None if means is None else np.ascontiguousarray(np.asarray(means, dtype=np.float64).reshape(6))
-    L = _lib()
-    scratch, ms = _G._ScratchBlocks(dev), _ms()
-    with torch.cuda.device(dev):
-        rc = L.gsr_icp_accumulate(scratch.cb, None, source.size(0), _G._ptr(source), ref.size(0), _G._ptr(ref),
-                                  _G._ptr(index), 1 if m is None else 2, None if m is None else _dptr(m), _dptr(sums),
-                                  ms, _G._stream(dev))
-    _check(L, rc)
-    return sums, _stats(ICP_STAGES, ms, scratch)
+    scratch, ms = ScratchBlocks(dev), stage_buffer(measure_stages)
+    call(dev, "gsr_icp_accumulate", scratch.cb, None, source.size(0), ptr(source), ref.size(0), ptr(ref), ptr(index),
+         1 if m is None else 2, None if m is None else f64ptr(m), f64ptr(sums), ms, stream(dev))
+    return sums, stage_stats(ICP_STAGES, ms, scratch)
 
 
 @torch.no_grad()
 def transform_points_(points, transform):
     """points [N,3] float64 <- the 4x4, in place: p' = ((r0 x + r1 y) + r2 z) + t.  -> stats."""
     who = "transform_points_"
-    _require_points(points, "points", who)
+    require_points(points, "points", who)
     if not points.is_contiguous():
         raise RuntimeError(f"{who}: `points` must be contiguous (it is changed in place)")
     T = _mat4(transform, who)
-    L = _lib()
-    ms = _ms()
-    with torch.cuda.device(points.device):
-        rc = L.gsr_points_transform(points.size(0), _G._ptr(points), _dptr(T), ms, _G._stream(points.device))
-    _check(L, rc)
-    return _stats(TRANSFORM_STAGES, ms)
+    ms = stage_buffer(measure_stages)
+    call(points.device, "gsr_points_transform", points.size(0), ptr(points), f64ptr(T), ms, stream(points.device))
+    return stage_stats(TRANSFORM_STAGES, ms)
 
 
 # ---- ICP ---------------------------------------------------------------------------------------------------------
@@ -316,7 +242,7 @@ def registration_icp(source, target_index, max_dist, max_iter, relative_fitness=
     -> dict: T [4,4] numpy, fitness, rmse, iterations, history [(fitness, rmse)], indices (the
     correspondence index tensor of every evaluation), stats."""
     who = "registration_icp"
-    _require_points(source, "source", who)
+    require_points(source, "source", who)
     if not isinstance(target_index, NearestIndex):
         raise RuntimeError(f"{who}: `target_index` must be a NearestIndex")
     src = source.contiguous().clone()
@@ -446,9 +372,9 @@ def tnt_fscore(vertices, faces, gt_points, crop, init_T, tau):
     float64, faces [F,3] int32 / int64, gt_points [G,3] float32 / float64.  -> dict: dTau, precision, recall,
     fscore (what metrics.json holds), the curves, counts, transformation, registrations, stats."""
     who = "tnt_fscore"
-    _require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
-    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
-    _require(gt_points, "gt_points", (torch.float32, torch.float64), 2, who)
+    require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
+    require(faces, "faces", (torch.int32, torch.int64), 2, who)
+    require(gt_points, "gt_points", (torch.float32, torch.float64), 2, who)
     if vertices.size(1) != 3 or faces.size(1) != 3 or gt_points.size(1) != 3:
         raise RuntimeError(f"{who}: `vertices`, `faces` and `gt_points` must have shapes (V, 3), (F, 3), (G, 3)")
     v, f = vertices.to(torch.float64), faces.long()
@@ -475,15 +401,11 @@ def _w2c_rows(w2c, who, batched):
 
 
 def _mesh_args(vertices, faces, who):
-    _require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
-    _require(faces, "faces", (torch.int32, torch.int64), 2, who)
+    require(vertices, "vertices", (torch.float32, torch.float64), 2, who)
+    require(faces, "faces", (torch.int32, torch.int64), 2, who)
     if vertices.size(1) != 3 or faces.size(1) != 3 or faces.device != vertices.device:
         raise RuntimeError(f"{who}: `vertices` and `faces` must have shapes (V, 3) and (F, 3) on one device")
     return vertices.to(torch.float32).contiguous(), faces.contiguous()
-
-
-def _fptr(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
 @torch.no_grad()
@@ -497,15 +419,13 @@ def render_mesh_depth(vertices, faces, w2c, H, W, fx, fy, cx, cy, znear=0.01, zf
     dev = v.device
     m = _w2c_rows(w2c, who, False)
     depth = torch.empty(int(H), int(W), dtype=torch.float32, device=dev)
-    L = _lib()
-    scratch, ms = _G._ScratchBlocks(dev), _ms()
+    scratch, ms = ScratchBlocks(dev), stage_buffer(measure_stages)
     ctr = (ctypes.c_ulonglong * 4)() if count else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_mesh_depth(scratch.cb, None, v.size(0), _G._ptr(v), f.size(0), _G._ptr(f),
-                              1 if f.dtype == torch.int64 else 0, _fptr(m), int(H), int(W), fx, fy, cx, cy, znear,
-                              zfar, _G._ptr(depth), ctr, ms, _G._stream(dev))
-    _check(L, rc)
-    return depth, _stats(RASTER_STAGES, ms, scratch, counters=None if ctr is None else dict(zip(RASTER_COUNTERS, ctr)))
+    call(dev, "gsr_mesh_depth", scratch.cb, None, v.size(0), ptr(v), f.size(0), ptr(f),
+         1 if f.dtype == torch.int64 else 0, f32ptr(m), int(H), int(W), fx, fy, cx, cy, znear, zfar, ptr(depth), ctr,
+         ms, stream(dev))
+    return depth, stage_stats(RASTER_STAGES, ms, scratch,
+                              counters=None if ctr is None else dict(zip(RASTER_COUNTERS, ctr)))
 
 
 @torch.no_grad()
@@ -519,16 +439,13 @@ def mesh_view_votes(vertices, faces, w2cs, H, W, fx, fy, cx, cy, znear=0.01, zfa
     dev = v.device
     m = _w2c_rows(w2cs, who, True)
     counts = torch.empty(v.size(0), dtype=torch.int32, device=dev)
-    L = _lib()
-    scratch, ms = _G._ScratchBlocks(dev), _ms()
+    scratch, ms = ScratchBlocks(dev), stage_buffer(measure_stages)
     ctr = (ctypes.c_ulonglong * 4)() if count else None
-    with torch.cuda.device(dev):
-        rc = L.gsr_mesh_view_votes(scratch.cb, None, v.size(0), _G._ptr(v), f.size(0), _G._ptr(f),
-                                   1 if f.dtype == torch.int64 else 0, m.shape[0], _fptr(m), int(H), int(W), fx, fy,
-                                   cx, cy, znear, zfar, eps, _G._ptr(counts), ctr, ms, _G._stream(dev))
-    _check(L, rc)
-    return counts, _stats(RASTER_STAGES, ms, scratch,
-                          counters=None if ctr is None else dict(zip(RASTER_COUNTERS, ctr)))
+    call(dev, "gsr_mesh_view_votes", scratch.cb, None, v.size(0), ptr(v), f.size(0), ptr(f),
+         1 if f.dtype == torch.int64 else 0, m.shape[0], f32ptr(m), int(H), int(W), fx, fy, cx, cy, znear, zfar, eps,
+         ptr(counts), ctr, ms, stream(dev))
+    return counts, stage_stats(RASTER_STAGES, ms, scratch,
+                               counters=None if ctr is None else dict(zip(RASTER_COUNTERS, ctr)))
 
 
 def read_cull_trajectory(path):

@@ -20,32 +20,13 @@ import ctypes
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _G
-from gsr_mesh import _Out, _require
+from diff_gaussian_rasterization._abi import Out, ScratchBlocks, call, ptr, record_stats, require, stage_buffer, stream
 
 KEY_BIAS = 1 << 20
 EXTRACT_STAGES = ("mark", "count", "vertices", "faces")
 # measurement hook (tools/bench_tsdf.py): when a dict, extract_triangle_mesh leaves its per-stage GPU
 # milliseconds and scratch bytes here (the timed call synchronises; leave None otherwise)
 last_call_stats = None
-
-
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_tsdf_bound", False):
-        vp, i, ll, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-        fp = ctypes.POINTER(ctypes.c_float)
-        L.gsr_tsdf_touch.restype = i
-        L.gsr_tsdf_touch.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, vp, i, i, fp, fp, f, f, f, f, ctypes.POINTER(ll), vp]
-        L.gsr_tsdf_lookup.restype = i
-        L.gsr_tsdf_lookup.argtypes = [ll, vp, ll, vp, vp, vp]
-        L.gsr_tsdf_integrate.restype = i
-        L.gsr_tsdf_integrate.argtypes = [ll, i, vp, vp, ll, f, vp, vp, vp, vp, vp, i, i, fp, fp, f, f, f, vp]
-        L.gsr_tsdf_extract.restype = i
-        L.gsr_tsdf_extract.argtypes = [_G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, _G._ALLOC, vp, ll, i, f, f, vp, vp,
-                                       vp, vp, vp, ctypes.POINTER(ll), ctypes.POINTER(ll), fp, vp]
-        L._tsdf_bound = True
-    return L
 
 
 def _camera(intrinsic, extrinsic, who):
@@ -154,7 +135,7 @@ class VoxelBlockGrid:
         self._capacity = cap
 
     def _check_coords(self, block_coords, who):
-        _require(block_coords, "block_coords", (torch.int32,), 2, who)
+        require(block_coords, "block_coords", (torch.int32,), 2, who)
         if block_coords.size(1) != 3:
             raise RuntimeError(f"{who}: `block_coords` must have shape (n, 3) (got {tuple(block_coords.shape)})")
         if block_coords.device != self.device:
@@ -170,12 +151,8 @@ class VoxelBlockGrid:
         """The position of every coordinate in the sorted index, -1 where the grid lacks the block."""
         n = block_coords.size(0)
         rank = torch.empty(n, dtype=torch.int32, device=self.device)
-        L = _lib()
-        with torch.cuda.device(self.device):
-            rc = L.gsr_tsdf_lookup(n, _G._ptr(block_coords), self._n, _G._ptr(self._sorted_keys), _G._ptr(rank),
-                                   _G._stream(self.device))
-        if rc != 0:
-            raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+        call(self.device, "gsr_tsdf_lookup", n, ptr(block_coords), self._n, ptr(self._sorted_keys), ptr(rank),
+             stream(self.device))
         return rank
 
     def _slots(self, block_coords, add):
@@ -203,7 +180,7 @@ class VoxelBlockGrid:
     # ---- the three stages --------------------------------------------------------------------
 
     def _check_depth(self, depth, who):
-        _require(depth, "depth", (torch.float32,), 2, who)
+        require(depth, "depth", (torch.float32,), 2, who)
         if depth.device != self.device:
             raise RuntimeError(f"{who}: `depth` must be on {self.device}")
         if depth.numel() == 0:
@@ -219,16 +196,11 @@ class VoxelBlockGrid:
         depth = self._check_depth(depth, who)
         _positive(who, depth_scale=depth_scale, depth_max=depth_max, trunc_voxel_multiplier=trunc_voxel_multiplier)
         k, e = _camera(intrinsic, extrinsic, who)
-        L = _lib()
-        out, scratch = _Out(self.device, torch.int32), _G._ScratchBlocks(self.device)
+        out, scratch = Out(self.device, torch.int32), ScratchBlocks(self.device)
         n = ctypes.c_longlong(0)
-        with torch.cuda.device(self.device):
-            rc = L.gsr_tsdf_touch(out.cb, None, scratch.cb, None, _G._ptr(depth), depth.size(0), depth.size(1), k, e,
-                                  float(depth_scale), float(depth_max),
-                                  self.voxel_size * float(trunc_voxel_multiplier),
-                                  self.voxel_size * self.block_resolution, ctypes.byref(n), _G._stream(self.device))
-        if rc != 0:
-            raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+        call(self.device, "gsr_tsdf_touch", out.cb, None, scratch.cb, None, ptr(depth), depth.size(0), depth.size(1),
+             k, e, float(depth_scale), float(depth_max), self.voxel_size * float(trunc_voxel_multiplier),
+             self.voxel_size * self.block_resolution, ctypes.byref(n), stream(self.device))
         return out.tensor[:3 * n.value].view(-1, 3)
 
     @torch.no_grad()
@@ -242,7 +214,7 @@ class VoxelBlockGrid:
         block_coords = self._check_coords(block_coords, who)
         _positive(who, depth_scale=depth_scale, depth_max=depth_max, trunc_voxel_multiplier=trunc_voxel_multiplier)
         if self.with_color:
-            _require(color, "color", (torch.float32,), 3, who)
+            require(color, "color", (torch.float32,), 3, who)
             if tuple(color.shape) != (depth.size(0), depth.size(1), 3) or color.device != self.device:
                 raise RuntimeError(f"{who}: `color` must have shape (H, W, 3) on {self.device} "
                                    f"(got {tuple(color.shape)} on {color.device})")
@@ -256,16 +228,10 @@ class VoxelBlockGrid:
         if torch.unique(pack_keys(block_coords)).numel() != n:
             raise RuntimeError(f"{who}: `block_coords` lists a block twice")
         slots = self._slots(block_coords, add=True)
-        L = _lib()
-        with torch.cuda.device(self.device):
-            rc = L.gsr_tsdf_integrate(n, self.block_resolution, _G._ptr(block_coords), _G._ptr(slots), self._n,
-                                      self.voxel_size, _G._ptr(self._tsdf), _G._ptr(self._weight),
-                                      _G._ptr(self._color) if self.with_color else None, _G._ptr(depth),
-                                      _G._ptr(color), depth.size(0), depth.size(1), k, e, float(depth_scale),
-                                      float(depth_max), self.voxel_size * float(trunc_voxel_multiplier),
-                                      _G._stream(self.device))
-        if rc != 0:
-            raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+        call(self.device, "gsr_tsdf_integrate", n, self.block_resolution, ptr(block_coords), ptr(slots), self._n,
+             self.voxel_size, ptr(self._tsdf), ptr(self._weight), ptr(self._color) if self.with_color else None,
+             ptr(depth), ptr(color), depth.size(0), depth.size(1), k, e, float(depth_scale), float(depth_max),
+             self.voxel_size * float(trunc_voxel_multiplier), stream(self.device))
 
     @torch.no_grad()
     def extract_triangle_mesh(self, weight_threshold=3.0):
@@ -273,29 +239,20 @@ class VoxelBlockGrid:
         weight_threshold -> (vertices [V,3] float32, faces [F,3] int64, colors
         [V,3] float32 or None without colour).  Vertices are shared between
         cubes; there are no vertex normals."""
-        global last_call_stats
         who = "extract_triangle_mesh"
         if isinstance(weight_threshold, bool) or not isinstance(weight_threshold, (int, float)) or \
                 not np.isfinite(weight_threshold):
             raise ValueError(f"{who}: `weight_threshold` must be a finite number (got {weight_threshold!r})")
         dev = self.device
-        L = _lib()
-        vout, cout, fout = _Out(dev, torch.float32), _Out(dev, torch.float32), _Out(dev, torch.int64)
-        scratch = _G._ScratchBlocks(dev)
+        vout, cout, fout = Out(dev, torch.float32), Out(dev, torch.float32), Out(dev, torch.int64)
+        scratch = ScratchBlocks(dev)
         V, F = ctypes.c_longlong(0), ctypes.c_longlong(0)
-        ms = (ctypes.c_float * 8)() if last_call_stats is not None else None
-        with torch.cuda.device(dev):
-            rc = L.gsr_tsdf_extract(vout.cb, None, cout.cb, None, fout.cb, None, scratch.cb, None, self._n,
-                                    self.block_resolution, self.voxel_size, float(weight_threshold),
-                                    _G._ptr(self._sorted_keys), _G._ptr(self._sorted_slots), _G._ptr(self._tsdf),
-                                    _G._ptr(self._weight), _G._ptr(self._color) if self.with_color else None,
-                                    ctypes.byref(V), ctypes.byref(F), ms, _G._stream(dev))
-        if rc != 0:
-            raise RuntimeError("gsr: " + L.gsr_last_error().decode())
-        if last_call_stats is not None:
-            last_call_stats.clear()
-            last_call_stats.update({k: float(ms[i]) for i, k in enumerate(EXTRACT_STAGES)},
-                                   scratch_bytes=[int(b.numel()) for b in scratch.blocks])
+        ms = stage_buffer(last_call_stats is not None)
+        call(dev, "gsr_tsdf_extract", vout.cb, None, cout.cb, None, fout.cb, None, scratch.cb, None, self._n,
+             self.block_resolution, self.voxel_size, float(weight_threshold), ptr(self._sorted_keys),
+             ptr(self._sorted_slots), ptr(self._tsdf), ptr(self._weight),
+             ptr(self._color) if self.with_color else None, ctypes.byref(V), ctypes.byref(F), ms, stream(dev))
+        record_stats(last_call_stats, EXTRACT_STAGES, ms, scratch)
         vertices = vout.tensor[:3 * V.value].view(-1, 3)
         faces = fout.tensor[:3 * F.value].view(-1, 3)
         colors = cout.tensor[:3 * V.value].view(-1, 3) if self.with_color else None
@@ -308,9 +265,9 @@ class VoxelBlockGrid:
         None.  Slot i is row i."""
         who = "from_arrays"
         for t, name, nd in ((tsdf, "tsdf", 2), (weight, "weight", 2)):
-            _require(t, name, (torch.float32,), nd, who)
+            require(t, name, (torch.float32,), nd, who)
         if color is not None:
-            _require(color, "color", (torch.float32,), 3, who)
+            require(color, "color", (torch.float32,), 3, who)
         g = cls(voxel_size, block_resolution, with_color=color is not None, device=tsdf.device,
                 block_count=max(int(tsdf.size(0)), 1))
         block_coords = g._check_coords(block_coords, who)

@@ -6,21 +6,9 @@ mean of the squared distances to its 3 nearest other points
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from diff_gaussian_rasterization import _C as _G
-
-
-def _lib():
-    L = _G._load()
-    if not getattr(L, "_knn_bound", False):
-        vp, i = ctypes.c_void_p, ctypes.c_int
-        L.gsr_knn_mean_dist.restype = i
-        L.gsr_knn_mean_dist.argtypes = [_G._ALLOC, vp, i, vp, vp, vp]
-        L._knn_bound = True
-    return L
+from diff_gaussian_rasterization._abi import Out, call, ptr, stream
 
 
 def distCUDA2(points):
@@ -30,15 +18,10 @@ def distCUDA2(points):
         raise RuntimeError("distCUDA2: `points` must be float32")
     if points.ndimension() != 2 or points.size(1) != 3:
         raise RuntimeError("distCUDA2: `points` must have shape (P, 3)")
-    L = _lib()
     P = points.size(0)
     pts = points.contiguous()
     means = torch.zeros(P, dtype=torch.float32, device=points.device)  # torch::full({P}, 0.0), spatial.cu:21
     if P:
-        scratch = _G._ByteBuffer(points.device)
-        with torch.cuda.device(points.device):
-            rc = L.gsr_knn_mean_dist(scratch.cb, None, P, ctypes.c_void_p(pts.data_ptr()),
-                                     ctypes.c_void_p(means.data_ptr()), _G._stream(points.device))
-        if rc != 0:
-            raise RuntimeError("gsr: " + L.gsr_last_error().decode())
+        scratch = Out(points.device, torch.uint8)
+        call(points.device, "gsr_knn_mean_dist", scratch.cb, None, P, ptr(pts), ptr(means), stream(points.device))
     return means

@@ -274,6 +274,48 @@ def gpu_entries_of(out, g, H, W):
     return int((plist[:int(ranges[:, 1].max())] == g).sum())
 
 
+def parse_header(path):
+    """The C ABI as include/gsr.h declares it, from the text of its extern "C" block (no compiler needed: the
+    header is regular).  -> (prototypes, structs): prototypes {name: (return type, [parameter type, ...])} in
+    the header's order, structs {name: [(member type, member name, array length or None), ...]}.  Types are
+    normalised: no `const`, no parameter name, single spaces, the stars attached ("float*", "long long")."""
+    import re
+
+    text = open(path).read()
+    text = text[text.index('extern "C" {'):text.rindex("#ifdef __cplusplus")]
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = "\n".join(ln for ln in text.split("\n")[1:] if not ln.lstrip().startswith("#"))
+
+    def ctype(decl):
+        """(type, name) of `const float* x`, `unsigned long long* counters`, `void* ctx`, `int key_bits[3]`."""
+        m = re.fullmatch(r"\s*(.*?)(\w+)\s*((?:\[\w+\])?)\s*", decl, flags=re.S)
+        t = re.sub(r"\bconst\b", " ", m.group(1))
+        t = re.sub(r"\s*\*\s*", "*", " ".join(t.split()))
+        return t, m.group(2), m.group(3)
+
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        members = []
+        for stmt in filter(str.strip, body.split(";")):
+            first, *more = stmt.split(",")  # `double bounds_min[3], bounds_max[3]`
+            t, n, arr = ctype(first)
+            for n, arr in [(n, arr)] + [ctype(t + " " + x)[1:] for x in more]:
+                members.append((t, n, int(arr[1:-1]) if arr else None))
+        structs[name] = members
+    text = re.sub(r"typedef\s+struct\s*\w*\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    text = re.sub(r"enum\s+\w+\s*\{.*?\}\s*;", " ", text, flags=re.S)
+    text = re.sub(r"typedef[^;]*;", " ", text)  # the two callback typedefs
+    prototypes = {}
+    for stmt in filter(str.strip, text.split(";")):
+        m = re.fullmatch(r"\s*(.*?)\b(gsr_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        assert m, f"not a prototype: {stmt.strip()[:80]!r}"
+        ret = ctype(m.group(1) + " _")[0]
+        params = [] if m.group(3).strip() == "void" else [ctype(p)[0] for p in m.group(3).split(",")]
+        assert m.group(2) not in prototypes, m.group(2)
+        prototypes[m.group(2)] = (ret, params)
+    return prototypes, structs
+
+
 def free_port() -> int:
     """A free TCP port for a process group's rendezvous, outside the kernel's ephemeral range: a port picked
     by binding to port 0 is an ephemeral one, and the gloo connections an earlier multi-rank test left in

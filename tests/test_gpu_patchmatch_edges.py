@@ -60,10 +60,8 @@ def setup(H, W, seed=0, **kw):
 
 def raw_terms(md, normal, pin, inside, consts):
     """gsr_patchmatch_terms_forward as _Terms.forward calls it: (w, flags, out) on the CPU."""
-    import gsr_patchmatch as PM
-    from diff_gaussian_rasterization import _C as _G
+    from diff_gaussian_rasterization import _C as _G, _abi
 
-    L = PM._lib()
     H, W = md.shape[-2:]
     t = [md.to(DEV).contiguous(), normal.to(DEV).contiguous(), pin.to(DEV).contiguous(), inside.to(DEV).contiguous()]
     w = torch.empty(H * W, dtype=torch.float32, device=DEV)
@@ -74,8 +72,7 @@ def raw_terms(md, normal, pin, inside, consts):
     scratch = _G._ByteBuffer(DEV)
     args = (H, W) + tuple(x.data_ptr() for x in t) + consts.ptrs() + (w.data_ptr(), flags.data_ptr(), gd.data_ptr(),
                                                                       gn.data_ptr())
-    with torch.cuda.device(DEV):
-        PM._check(L, L.gsr_patchmatch_terms_forward(scratch.cb, None, *args, out.data_ptr(), _G._stream(DEV)))
+    _abi.call(DEV, "gsr_patchmatch_terms_forward", scratch.cb, None, *args, out.data_ptr(), _G._stream(DEV))
     torch.cuda.synchronize()
     return w.cpu().numpy(), flags.cpu().numpy(), out.cpu().numpy()
 
