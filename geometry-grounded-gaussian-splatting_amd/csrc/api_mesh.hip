@@ -1,6 +1,7 @@
 // api_mesh.hip — the C ABI (include/gsr.h) of the mesh path: marching tetrahedra (tetmesh.hip), the
-// mesh clean-up (meshclean.hip) and TSDF fusion with marching cubes (tsdf.hip).  Host orchestration
-// only: each call sizes its outputs from counts it reads back through one pinned slot (Readback).
+// extraction sweep around `integrate` (fieldsweep.hip), the mesh clean-up (meshclean.hip) and TSDF
+// fusion with marching cubes (tsdf.hip).  Host orchestration only: each call sizes its outputs from
+// counts it reads back through one pinned slot (Readback); the sweep's three entries read nothing back.
 #include "gsr_api_common.h"
 
 using namespace gsr;
@@ -71,6 +72,47 @@ int gsr_marching_tetrahedra(gsr_alloc_fn edge_alloc, void* edge_ctx, gsr_alloc_f
     *num_edges = (long long)E;
     *num_faces = (long long)F;
     return GSR_OK;
+}
+
+int gsr_field_view_update(long long N, const float* points, const float* alpha, const uint8_t* inside, const float* R,
+                          const float* T, double Fx, double Fy, double Cx, double Cy, int W, int H, const float* mask,
+                          float* weight, uint8_t* seen, void* stream_ptr) {
+    if (N < 0 || N > kFieldMaxN) return fail(GSR_ERR_ARGS, "field_view_update: invalid size");
+    if (mask && (W < 1 || H < 1)) return fail(GSR_ERR_ARGS, "field_view_update: a mask needs W, H >= 1");
+    if (N == 0) return GSR_OK;
+    if (!alpha || !inside || !weight || !seen) return fail(GSR_ERR_ARGS, "field_view_update: missing buffer");
+    if (mask && (!points || !R || !T)) return fail(GSR_ERR_ARGS, "field_view_update: a mask needs points, R and T");
+    FieldView v{};
+    if (mask) {
+        for (int k = 0; k < 9; k++) v.r[k] = R[k];
+        for (int k = 0; k < 3; k++) v.t[k] = T[k];
+        // the reference's constants: float64 on the host, then rounded (mesh_extract_tetrahedra.py:50-57)
+        v.c[0] = (float)((Cx * 2.0 + 1.0) / W - 1.0), v.c[1] = (float)((Cy * 2.0 + 1.0) / H - 1.0);
+        v.s[0] = (float)(Fx * 2.0 / W), v.s[1] = (float)(Fy * 2.0 / H);
+        v.W = W, v.H = H;
+    }
+    hipError_t e = launch_field_view_update(v, N, points, alpha, inside, mask, weight, seen, (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "field view update", e);
+}
+
+int gsr_field_finish(long long N, const float* weight, const uint8_t* seen, float* sdf, uint8_t* valid,
+                     void* stream_ptr) {
+    if (N < 0 || N > kFieldMaxN) return fail(GSR_ERR_ARGS, "field_finish: invalid size");
+    if (N == 0) return GSR_OK;
+    if (!weight || !seen || !sdf || !valid) return fail(GSR_ERR_ARGS, "field_finish: missing buffer");
+    hipError_t e = launch_field_finish(N, weight, seen, sdf, valid, (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "field finish", e);
+}
+
+int gsr_field_bisect_step(long long E, void* left_points, void* right_points, int points_float64, float* left_sdf,
+                          float* right_sdf, const float* mid_sdf, void* mid_points, void* stream_ptr) {
+    if (E < 0 || E > kFieldMaxN) return fail(GSR_ERR_ARGS, "field_bisect_step: invalid size");
+    if (E == 0) return GSR_OK;
+    if (!left_points || !right_points || !left_sdf || !right_sdf || !mid_sdf || !mid_points)
+        return fail(GSR_ERR_ARGS, "field_bisect_step: missing buffer");
+    hipError_t e = launch_field_bisect(E, left_points, right_points, points_float64 != 0, left_sdf, right_sdf, mid_sdf,
+                                       mid_points, (hipStream_t)stream_ptr);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "field bisect step", e);
 }
 
 int gsr_mesh_clusters(gsr_alloc_fn count_alloc, void* count_ctx, gsr_alloc_fn area_alloc, void* area_ctx,

@@ -571,6 +571,23 @@ hipError_t launch_raster_finish(const RasterCamera& c, const MeshRasterState& s,
 hipError_t launch_view_vote(const RasterCamera& c, float eps, long long V, const float* vertices,
                             const MeshRasterState& s, int* counts, hipStream_t stream);
 
+// The tetrahedral extraction sweep around `integrate` (fieldsweep.hip): per-view update of a chunk's running
+// minimum, the chunk's finish, one bisection step.  No scratch, no readback.
+constexpr long long kFieldMaxN = 0x7fffffffll * 256;  // one point or edge per lane, 256 lanes per block
+struct FieldView {   // by value into the kernel
+    float r[9];      // R, row-major: camera = points @ R + t
+    float t[3];
+    float c[2], s[2];  // grid_sample coordinates c + s * (camera.xy / camera.z)
+    int W, H;        // the mask plane
+};
+hipError_t launch_field_view_update(const FieldView& v, long long N, const float* points, const float* alpha,
+                                    const uint8_t* inside, const float* mask, float* weight, uint8_t* seen,
+                                    hipStream_t stream);
+hipError_t launch_field_finish(long long N, const float* weight, const uint8_t* seen, float* sdf, uint8_t* valid,
+                               hipStream_t stream);
+hipError_t launch_field_bisect(long long E, void* left, void* right, bool f64, float* left_sdf, float* right_sdf,
+                               const float* mid_sdf, void* mid, hipStream_t stream);
+
 // densify.hip: densify / prune plan and gather, radix-select quantile, 3D filter, opacity reset
 constexpr int kMaxDensifyParams = 16;
 enum : int { kDensifyCopy = 0, kDensifyXyz = 1, kDensifyScaling = 2 };

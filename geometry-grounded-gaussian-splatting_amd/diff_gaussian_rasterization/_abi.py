@@ -100,8 +100,11 @@ SIGNATURES = {
     "gsr_depth_to_normal_backward": (i, [vp, i, i, f, f, f, f, vp, vp, vp]),
     # initial scales
     "gsr_knn_mean_dist": (i, A + [i, vp, vp, vp]),
-    # marching tetrahedra and mesh clean-up
+    # marching tetrahedra, the extraction sweep and mesh clean-up
     "gsr_marching_tetrahedra": (i, A * 3 + [ll, ll, vp, i, vp, vp, llp, llp, fp, vp]),
+    "gsr_field_view_update": (i, [ll, vp, vp, vp, fp, fp, d, d, d, d, i, i, vp, vp, vp, vp]),
+    "gsr_field_finish": (i, [ll] + [vp] * 5),
+    "gsr_field_bisect_step": (i, [ll, vp, vp, i] + [vp] * 5),
     "gsr_mesh_clusters": (i, A * 3 + [ll, ll, vp, i, vp, vp, llp, fp, vp]),
     "gsr_mesh_filter": (i, A * 3 + [ll, ll, ll, vp, vp, i, vp, vp, vp, llp, llp, vp]),
     # TSDF fusion and marching cubes

@@ -1,8 +1,9 @@
 """Tetrahedral mesh extraction (mesh_extract_tetrahedra.py:18-179 and
 utils/tetmesh.py of the reference) over the C ABI: marching tetrahedra in HIP
 (gsr_marching_tetrahedra, csrc/tetmesh.hip), the driver around
-gaussian_renderer.integrate, and the mesh clean-up (gsr_mesh_clusters and
-gsr_mesh_filter, csrc/meshclean.hip).
+gaussian_renderer.integrate (with sweep="hip" its per-view glue and its
+bisection step are the three kernels of csrc/fieldsweep.hip), and the mesh
+clean-up (gsr_mesh_clusters and gsr_mesh_filter, csrc/meshclean.hip).
 
     points = gsr_scene.tetra_points(inp); scale = gsr_scene.tetra_points_scale(inp)
     cells = <the caller's Delaunay triangulation of points, [T, 4]>
@@ -26,8 +27,8 @@ import ctypes
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization._abi import (Out, ScratchBlocks, call, ptr, record_stats, require, require_mesh,
-                                              stage_buffer, stream)
+from diff_gaussian_rasterization._abi import (Out, ScratchBlocks, call, f32ptr, ptr, record_stats, require,
+                                              require_mesh, stage_buffer, stream)
 
 STAGES = ("flags", "count", "emit", "sort", "ranks", "edges", "faces")
 # measurement hook (tools/bench_tetmesh.py): when a dict, every call leaves its per-stage GPU
@@ -170,15 +171,116 @@ def _view_mask(view, points, inside):
     return (sampled.squeeze() > 0.5) & inside
 
 
-@torch.no_grad()
-def alpha_cull_sdf(points, views, pc, pipe, kernel_size, chunk=10_000_000):
-    """mesh_extract_tetrahedra.py:64-87: sdf = 0.5 - the smallest integrated
-    opacity over the views that see the point (inside the image and, where a
-    view has a gt_mask, on it); 0.5 where no view does.  -> (sdf [N], any_valid [N])."""
+def _check_sweep(sweep, who):
+    if sweep not in ("torch", "hip"):
+        raise ValueError(f"{who}: `sweep` must be \"torch\" or \"hip\" (got {sweep!r})")
+
+
+def _sweep_views(views, device):
+    """What gsr_field_view_update (csrc/fieldsweep.hip) takes of every view, read and uploaded once per
+    sweep rather than per chunk: [(view, None)] without a gt_mask, else (view, (R [9] and T [3] host
+    float32, Fx, Fy, Cx, Cy, W, H, the mask plane [H,W] float32 on `device`))."""
+    out = []
+    for view in views:
+        mask = getattr(view, "gt_mask", None)
+        if mask is None:
+            out.append((view, None))
+            continue
+        W, H = int(view.image_width), int(view.image_height)
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (1, H, W):
+            raise RuntimeError(f"alpha_cull_sdf: a view's `gt_mask` must be a tensor of shape (1, {H}, {W})")
+        R = np.ascontiguousarray(torch.as_tensor(view.R).to(torch.float32).cpu().numpy())
+        T = np.ascontiguousarray(torch.as_tensor(view.T).to(torch.float32).cpu().numpy())
+        if R.shape != (3, 3) or T.shape != (3,):
+            raise RuntimeError("alpha_cull_sdf: a view's `R` must have shape (3, 3) and its `T` shape (3,)")
+        plane = mask.to(device=device, dtype=torch.float32).reshape(H, W).contiguous()
+        out.append((view, (R, T, float(view.Fx), float(view.Fy), float(view.Cx), float(view.Cy), W, H, plane)))
+    return out
+
+
+def _alpha_cull_sdf_hip(points, sweep_views, pc, pipe, kernel_size, chunk):
+    """alpha_cull_sdf over _sweep_views' list with the running minimum on the device: per chunk and view
+    one `integrate` and one gsr_field_view_update, gsr_field_finish at the chunk's end.  The chunk's
+    weight / seen live in its slice of the two results, so the sweep allocates nothing else."""
     from gaussian_renderer import integrate
 
+    who = "alpha_cull_sdf"
+    require(points, "points", (torch.float32,), 2, who)
+    if points.size(1) != 3:
+        raise RuntimeError(f"{who}: `points` must have shape (N, 3) (got {tuple(points.shape)})")
+    dev, points = points.device, points.contiguous()
+    sdf = torch.empty(points.shape[0], dtype=torch.float32, device=dev)
+    valid = torch.empty(points.shape[0], dtype=torch.bool, device=dev)
+    lo = 0
+    for part in torch.chunk(points, points.shape[0] // chunk + 1):
+        n = part.shape[0]
+        weight, seen = sdf[lo:lo + n], valid[lo:lo + n].view(torch.uint8)
+        lo += n
+        if n == 0:
+            continue
+        weight.fill_(1)
+        seen.zero_()
+        for view, cam in sweep_views:
+            ret = integrate(part, view, pc, pipe, kernel_size)
+            alpha, inside = ret["alpha_integrated"], ret["inside"]
+            require(alpha, "alpha_integrated", (torch.float32,), 1, who)
+            require(inside, "inside", (torch.bool, torch.uint8), 1, who)
+            if alpha.shape[0] != n or inside.shape[0] != n:
+                raise RuntimeError(f"{who}: `integrate` must return one value per point")
+            alpha, inside = alpha.contiguous(), inside.contiguous()
+            if cam is None:
+                call(dev, "gsr_field_view_update", n, None, ptr(alpha), ptr(inside), None, None, 0.0, 0.0, 0.0, 0.0,
+                     0, 0, None, ptr(weight), ptr(seen), stream(dev))
+            else:
+                R, T, Fx, Fy, Cx, Cy, W, H, plane = cam
+                call(dev, "gsr_field_view_update", n, ptr(part), ptr(alpha), ptr(inside), f32ptr(R), f32ptr(T), Fx,
+                     Fy, Cx, Cy, W, H, ptr(plane), ptr(weight), ptr(seen), stream(dev))
+        call(dev, "gsr_field_finish", n, ptr(weight), ptr(seen), ptr(weight), ptr(seen), stream(dev))
+    return sdf, valid
+
+
+@torch.no_grad()
+def bisect_step(left_points, right_points, left_sdf, right_sdf, mid_sdf, mid_points):
+    """One step of mesh_extract_tetrahedra.py:155-163 in place (gsr_field_bisect_step,
+    csrc/fieldsweep.hip): where `mid_sdf` [E], the field at (left + right) * 0.5, has `left_sdf`'s sign the
+    midpoint replaces the left end, otherwise (0 included) the right end; `mid_points` [E,3] receives the
+    new (left + right) * 0.5.  Points [E,3] float32 or float64, sdf [E] or [E,1] float32, all contiguous
+    (they are updated in place).  Runs on the current stream."""
+    who = "bisect_step"
+    require(left_points, "left_points", (torch.float32, torch.float64), 2, who)
+    E, dev = left_points.size(0), left_points.device
+    for t, name in ((left_points, "left_points"), (right_points, "right_points"), (mid_points, "mid_points")):
+        require(t, name, (left_points.dtype,), 2, who)
+        if tuple(t.shape) != (E, 3):
+            raise RuntimeError(f"{who}: `{name}` must have shape ({E}, 3) (got {tuple(t.shape)})")
+    for t, name in ((left_sdf, "left_sdf"), (right_sdf, "right_sdf"), (mid_sdf, "mid_sdf")):
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
+                or tuple(t.shape) not in ((E,), (E, 1))):
+            raise RuntimeError(f"{who}: `{name}` must be a float32 HIP tensor of shape ({E},) or ({E}, 1)")
+    for t in (left_points, right_points, mid_points, left_sdf, right_sdf, mid_sdf):
+        if t.device != dev or not t.is_contiguous():
+            raise RuntimeError(f"{who}: the buffers must be contiguous and on one device")
+    call(dev, "gsr_field_bisect_step", E, ptr(left_points), ptr(right_points),
+         int(left_points.dtype == torch.float64), ptr(left_sdf), ptr(right_sdf), ptr(mid_sdf), ptr(mid_points),
+         stream(dev))
+
+
+@torch.no_grad()
+def alpha_cull_sdf(points, views, pc, pipe, kernel_size, chunk=10_000_000, sweep="torch"):
+    """mesh_extract_tetrahedra.py:64-87: sdf = 0.5 - the smallest integrated
+    opacity over the views that see the point (inside the image and, where a
+    view has a gt_mask, on it); 0.5 where no view does.  -> (sdf [N], any_valid [N]).
+    sweep="hip" keeps the running minimum on the device and folds every view
+    in with one kernel (gsr_field_view_update / gsr_field_finish)
+    instead of the torch formulation; the results are the same bits as long as
+    no mask sample lies within rounding of 0.5."""
+    from gaussian_renderer import integrate
+
+    _check_sweep(sweep, "alpha_cull_sdf")
     if not isinstance(points, torch.Tensor) or not points.is_cuda:
         raise RuntimeError("alpha_cull_sdf: `points` must be a HIP device tensor")
+    if sweep == "hip":
+        return _alpha_cull_sdf_hip(points, _sweep_views(views, points.device), pc, pipe, kernel_size, chunk)
     sdfs, valids = [], []
     for part in torch.chunk(points, points.shape[0] // chunk + 1):
         weight = torch.ones(part.shape[0], dtype=torch.float32, device=points.device)
@@ -195,7 +297,8 @@ def alpha_cull_sdf(points, views, pc, pipe, kernel_size, chunk=10_000_000):
 
 
 @torch.no_grad()
-def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_binary_steps=10, cluster_to_keep=None):
+def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_binary_steps=10, sweep="torch",
+                 cluster_to_keep=None):
     """mesh_extract_tetrahedra.py:123-169: the level set sdf = 0 of
     alpha_cull_sdf over the tets `cells` [T,4] of `points` [V,3]
     (`points_scale` [V,1]: gsr_scene.tetra_points_scale), every vertex bisected
@@ -203,8 +306,17 @@ def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_bi
     the two ends' scales and the faces that use them are dropped.
     -> vertices [N,3] float32, faces [M,3] int64 (the geometry of recon.ply).
     With an integer `cluster_to_keep` the result goes through
-    post_process_mesh (the geometry of recon_post.ply)."""
-    sdf, valid = alpha_cull_sdf(points, views, pc, pipe, kernel_size)
+    post_process_mesh (the geometry of recon_post.ply).  sweep="hip" runs all
+    eleven sweeps as alpha_cull_sdf(sweep="hip") does, the views read once, and
+    the bisection in place with bisect_step (no [E,3] temporaries per step)."""
+    _check_sweep(sweep, "extract_mesh")
+    if sweep == "hip":
+        if not isinstance(points, torch.Tensor) or not points.is_cuda:
+            raise RuntimeError("extract_mesh: `points` must be a HIP device tensor")
+        sweep_views = _sweep_views(views, points.device)
+        sdf, valid = _alpha_cull_sdf_hip(points, sweep_views, pc, pipe, kernel_size, 10_000_000)
+    else:
+        sdf, valid = alpha_cull_sdf(points, views, pc, pipe, kernel_size)
     verts_list, scale_list, faces_list, _ = marching_tetrahedra(points[None], cells, sdf[None], points_scale[None], valid[None])
     end_points, end_sdf = verts_list[0]
     end_scales, faces = scale_list[0], faces_list[0]
@@ -213,7 +325,11 @@ def extract_mesh(points, points_scale, cells, views, pc, pipe, kernel_size, n_bi
     distance = torch.norm(left_points - right_points, dim=-1)
     scale = end_scales[:, 0, 0] + end_scales[:, 1, 0]
     vertices = (left_points + right_points) * 0.5
-    for _ in range(n_binary_steps if vertices.shape[0] else 0):
+    if sweep == "hip":  # `vertices` is the midpoint buffer: a step's query points, then its result
+        for _ in range(n_binary_steps if vertices.shape[0] else 0):
+            mid_sdf = _alpha_cull_sdf_hip(vertices, sweep_views, pc, pipe, kernel_size, 10_000_000)[0]
+            bisect_step(left_points, right_points, left_sdf, right_sdf, mid_sdf, vertices)
+    for _ in range(n_binary_steps if vertices.shape[0] and sweep == "torch" else 0):
         mid_points = (left_points + right_points) * 0.5
         mid_sdf = alpha_cull_sdf(mid_points, views, pc, pipe, kernel_size)[0].unsqueeze(-1)
         # a midpoint on the left end's side replaces it; one with sdf exactly 0 replaces the right end

@@ -572,6 +572,51 @@ int gsr_marching_tetrahedra(gsr_alloc_fn edge_alloc, void* edge_ctx, gsr_alloc_f
                             long long* num_edges, long long* num_faces, float* stage_ms, void* stream);
 
 /*
+ * The sweep of the tetrahedral extraction around gsr_integrate_forward
+ * (mesh_extract_tetrahedra.py:44-87 and :155-163).  Additive: the
+ * ABI version is unchanged.  All buffers are device memory unless noted; the
+ * three calls launch one kernel each on `stream`, need no scratch, read
+ * nothing back and do not synchronise.  A size of 0 is a valid no-op, a
+ * negative size or a NULL required buffer is GSR_ERR_ARGS and touches nothing.
+ *
+ * gsr_field_view_update folds one view into the running state of N points:
+ * ok = inside and, with a mask, sample > 0.5; where ok, seen = 1 and weight =
+ * alpha when alpha < weight (or alpha is NaN).  alpha [N] fp32 and inside [N]
+ * (one byte per point, non-zero = set) are gsr_integrate_forward's outputs
+ * (alpha = 1 - transmittance); weight [N] fp32 and seen [N] uint8 (0 or 1)
+ * are updated in place, the caller starts them at 1 and 0.  mask [H,W] fp32 may
+ * be NULL (no mask test; points, R, T and the camera numbers are then unused
+ * and points, R, T may be NULL).  With a mask, for the points with inside set
+ * only (so a point at or behind the near plane never divides): points [N,3]
+ * fp32; R [9] and T [3] are HOST fp32, camera = points @ R + T with R
+ * row-major; uv = c + s * (camera.xy / camera.z) with c = ((Cx 2 + 1) / W - 1,
+ * (Cy 2 + 1) / H - 1) and s = (Fx 2 / W, Fy 2 / H) computed in float64 and
+ * rounded to fp32; sample = the bilinear sample of the mask at uv as
+ * torch.nn.functional.grid_sample takes it (align_corners=True, zeros
+ * padding).  fp32 in the fixed operation order of DESIGN 6k without fused
+ * multiply-add.  W, H < 1 with a mask is GSR_ERR_ARGS.
+ *
+ * gsr_field_finish ends a chunk: sdf [N] fp32 = 0.5 - (seen ? weight : 0),
+ * valid [N] (one byte, 0 or 1) = seen.  sdf may be weight and valid may be
+ * seen.
+ *
+ * gsr_field_bisect_step is one bisection step over E edges, in place:
+ * left_points, right_points [E,3] fp32 (points_float64 == 0) or fp64,
+ * left_sdf, right_sdf [E] fp32, mid_sdf [E] fp32 the field at
+ * (left + right) * 0.5.  Where mid_sdf and left_sdf are both < 0 or both > 0
+ * the midpoint and mid_sdf replace the left end, otherwise (a mid_sdf of
+ * exactly 0 and NaN included) the right end; mid_points [E,3] (written only,
+ * a buffer of its own) = the new (left + right) * 0.5: the next step's query
+ * points and, after the last step, the vertices.
+ */
+int gsr_field_view_update(long long N, const float* points, const float* alpha, const uint8_t* inside, const float* R,
+                          const float* T, double Fx, double Fy, double Cx, double Cy, int W, int H, const float* mask,
+                          float* weight, uint8_t* seen, void* stream);
+int gsr_field_finish(long long N, const float* weight, const uint8_t* seen, float* sdf, uint8_t* valid, void* stream);
+int gsr_field_bisect_step(long long E, void* left_points, void* right_points, int points_float64, float* left_sdf,
+                          float* right_sdf, const float* mid_sdf, void* mid_points, void* stream);
+
+/*
  * Mesh clean-up (the reference's post_process_mesh,
  * mesh_extract_tetrahedra.py:18-40, which runs open3d on the CPU), in two
  * calls.
