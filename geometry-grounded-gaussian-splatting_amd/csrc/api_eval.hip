@@ -1,5 +1,6 @@
 // api_eval.hip — the C ABI (include/gsr.h) of the DTU Chamfer evaluation (pointeval.hip): surface
-// sampling, radius thinning and nearest point.  Host orchestration only.
+// sampling, radius thinning and nearest point; and of the image-quality evaluation (imgmetric.hip):
+// 8-bit quantisation, L1, MSE and per-image SSIM.  Host orchestration only.
 #include <float.h>
 #include <math.h>
 
@@ -158,6 +159,45 @@ int gsr_points_nearest(gsr_alloc_fn scratch_alloc, void* scratch_ctx, long long 
     GSR_TIMED(times, 2, launch_nearest_qsort(Q, query, grid, ns, stream), "query sort");
     GSR_TIMED(times, 3, launch_nearest_search(Q, query, R, grid, ns, max_dist, dist, stream), "nearest search");
     GSR_CHECK(times.collect(), "stage times");
+    return GSR_OK;
+}
+
+int gsr_image_quantize8(long long N, int C, int H, int W, const float* image, uint8_t* out, void* stream_ptr) {
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (N < 0 || C <= 0 || H <= 0 || W <= 0) return fail(GSR_ERR_ARGS, "image_quantize8: invalid sizes");
+    if (N == 0) return GSR_OK;
+    if (!image || !out) return fail(GSR_ERR_ARGS, "image_quantize8: missing buffer");
+    if ((double)N * C * H * W >= 1099511627776.0) return fail(GSR_ERR_ARGS, "image_quantize8: 2^40 or more values");
+    if ((uintptr_t)out & 3) return fail(GSR_ERR_ARGS, "image_quantize8: `out` must be 4-byte aligned");
+    GSR_CHECK(launch_image_quantize8(N, C, H, W, image, out, stream), "image quantize8");
+    return GSR_OK;
+}
+
+int gsr_image_metrics(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int N, int C, int H, int W, int quantize,
+                      int with_ssim, const float* render, const float* gt, uint8_t* render_bytes, uint8_t* gt_bytes,
+                      double* out, void* stream_ptr) {
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    if (N < 0 || C <= 0 || H <= 0 || W <= 0) return fail(GSR_ERR_ARGS, "image_metrics: invalid sizes");
+    if (with_ssim && (H < 11 || W < 11))
+        return fail(GSR_ERR_ARGS, "image_metrics: SSIM needs H and W of at least 11 (no 11 x 11 window fits)");
+    if (N == 0) return GSR_OK;
+    if (N > 65535) return fail(GSR_ERR_ARGS, "image_metrics: more than 65535 images in one call");
+    if ((double)C * H * W >= 2147483648.0) return fail(GSR_ERR_ARGS, "image_metrics: 2^31 or more values per image");
+    if (!render || !gt || !out) return fail(GSR_ERR_ARGS, "image_metrics: missing buffer");
+    if (!scratch_alloc) return fail(GSR_ERR_ARGS, "image_metrics: missing allocator");
+    if (render_bytes || gt_bytes) {
+        if (!quantize) return fail(GSR_ERR_ARGS, "image_metrics: byte images are written in quantised mode only");
+        if (C > 4) return fail(GSR_ERR_ARGS, "image_metrics: byte images have at most 4 channels");
+        if (((uintptr_t)render_bytes | (uintptr_t)gt_bytes) & 3)
+            return fail(GSR_ERR_ARGS, "image_metrics: byte images must be 4-byte aligned");
+    }
+    ImageMetricsState st;
+    if (int rc = carve_alloc(scratch_alloc, scratch_ctx, "image_metrics: scratch allocation failed",
+                             carve_image_metrics, N, C, H, W, with_ssim, st))
+        return rc;
+    GSR_CHECK(launch_image_metrics(N, C, H, W, quantize, with_ssim, render, gt, render_bytes, gt_bytes, st, out,
+                                   stream),
+              "image metrics");
     return GSR_OK;
 }
 

@@ -632,4 +632,17 @@ hipError_t launch_chunk_order(uint32_t bound, const uint32_t* n_dev, const uint3
                               hipStream_t stream);
 uint32_t sample_chunk_bound(int PN, uint32_t tiles);
 
+// imgmetric.hip: 8-bit quantisation, L1 / MSE and the per-image "valid" SSIM of a batch of image pairs
+struct ImageMetricsState {  // per (image, channel, tile) partials
+    double* p_ssim;
+    unsigned long long* p_s1;
+    unsigned long long* p_s2;
+};
+size_t carve_image_metrics(void* base, int N, int C, int H, int W, int with_ssim, ImageMetricsState& st);
+hipError_t launch_image_metrics(int N, int C, int H, int W, int quantize, int with_ssim, const float* render,
+                                const float* gt, uint8_t* render_bytes, uint8_t* gt_bytes,
+                                const ImageMetricsState& st, double* out, hipStream_t stream);
+hipError_t launch_image_quantize8(long long N, int C, int H, int W, const float* image, uint8_t* out,
+                                  hipStream_t stream);
+
 }  // namespace gsr

@@ -153,6 +153,9 @@ SIGNATURES = {
     "gsr_quantile": (i, [ll] + [vp] * 5),
     "gsr_filter_3d": (i, [ll, vp, i, vp, f, vp, vp, vp]),
     "gsr_reset_opacity": (i, [ll] + [vp] * 7),
+    # image-quality evaluation
+    "gsr_image_quantize8": (i, [ll, i, i, i, vp, vp, vp]),
+    "gsr_image_metrics": (i, A + [i] * 6 + [vp] * 6),
     # status
     "gsr_last_error": (c_char_p, []),
     "gsr_abi_version": (i, []),

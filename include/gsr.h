@@ -1138,6 +1138,38 @@ int gsr_filter_3d(long long P, const float* xyz, int n_cam, const float* cameras
 int gsr_reset_opacity(long long P, const float* scaling, const float* opacity, const float* filter_3D,
                       float* opacity_out, float* exp_avg_out, float* exp_avg_sq_out, void* stream);
 
+/*
+ * Image-quality evaluation (the reference's render.py -> metric.py, and the
+ * test report of train.py:332-365).  Images are [N,C,H,W] fp32 planes.
+ *
+ * gsr_image_quantize8: the byte image torchvision's save_image hands to the
+ * PNG writer, out [N,H,W,C] (4-byte aligned):
+ *   byte = trunc(clamp(fl(fl(x * 255) + 0.5), 0, 255)),
+ * the multiply and the add rounded separately in fp32 (never fused); NaN and
+ * -inf give 0, +inf 255.
+ *
+ * gsr_image_metrics: out [N,3] float64 (device) receives per image
+ * {l1, mse, ssim} of render against gt, each input read once.
+ *   quantize != 0: both images go through the rule above and are compared as
+ *     fl(byte / 255), what PIL and to_tensor read back; the sums are exact
+ *     integers, l1 = S1 / (255 n), mse = S2 / (65025 n), n = C H W.
+ *     render_bytes / gt_bytes (each NULL or [N,H,W,C], 4-byte aligned, C <= 4)
+ *     receive the byte images from the same read.
+ *   quantize == 0: both images are clamped to [0, 1], differences in fp32,
+ *     sums in float64.
+ *   with_ssim != 0: ssim is the mean of the reference's SSIM map (11 x 11
+ *     Gaussian window, sigma 1.5, C1 = 1e-4, C2 = 9e-4) over the C (H-10)
+ *     (W-10) windows inside that image, on the compared values; needs H, W
+ *     >= 11.  Otherwise ssim = 0 and any H, W >= 1 is accepted.
+ * Per-workgroup partials and a fixed-order finish per image: no atomics, an
+ * image's numbers do not depend on the rest of the batch.  Asynchronous on
+ * `stream`; PSNR = -10 log10(mse) is the caller's.
+ */
+int gsr_image_quantize8(long long N, int C, int H, int W, const float* image, uint8_t* out, void* stream);
+int gsr_image_metrics(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int N, int C, int H, int W, int quantize,
+                      int with_ssim, const float* render, const float* gt, uint8_t* render_bytes, uint8_t* gt_bytes,
+                      double* out, void* stream);
+
 /* Human-readable message for the last non-OK status on this thread. */
 const char* gsr_last_error(void);
 
