@@ -645,4 +645,13 @@ hipError_t launch_image_metrics(int N, int C, int H, int W, int quantize, int wi
 hipError_t launch_image_quantize8(long long N, int C, int H, int W, const float* image, uint8_t* out,
                                   hipStream_t stream);
 
+// viewprep.hip: Pillow's 8-bit bicubic resample (one pass along one axis) and the float planes of a view
+int resample_ksize(int in_size, int out_size);
+void resample_coeffs(int in_size, int out_size, int32_t* k, int32_t* bounds);  // host: k [out][ksize], bounds [out][2]
+// axis 1: along W, axis 0: along H; k tap-major [ksize][out_size] and bounds [out_size][2] on the device
+hipError_t launch_image_resample8(long long N, int H, int W, int C, int axis, int out_size, const uint8_t* in,
+                                  uint8_t* out, const int32_t* k, const int32_t* bounds, hipStream_t stream);
+hipError_t launch_view_planes(long long N, int H, int W, const uint8_t* rgb, const uint8_t* mask, float* original,
+                              float* gray, float* gt_mask, hipStream_t stream);
+
 }  // namespace gsr

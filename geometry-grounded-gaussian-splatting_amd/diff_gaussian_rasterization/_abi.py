@@ -156,6 +156,11 @@ SIGNATURES = {
     # image-quality evaluation
     "gsr_image_quantize8": (i, [ll, i, i, i, vp, vp, vp]),
     "gsr_image_metrics": (i, A + [i] * 6 + [vp] * 6),
+    # view preparation
+    "gsr_resample_ksize": (i, [i, i]),
+    "gsr_resample_coeffs": (i, [i, i, ip, ip]),
+    "gsr_image_resample8": (i, [ll, i, i, i, i, i, vp, vp, vp, vp, vp]),
+    "gsr_view_planes": (i, [ll, i, i] + [vp] * 6),
     # status
     "gsr_last_error": (c_char_p, []),
     "gsr_abi_version": (i, []),

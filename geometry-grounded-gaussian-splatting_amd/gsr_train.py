@@ -66,6 +66,7 @@ class TrainView:
     gray_image: torch.Tensor | None = None
     gt_mask: torch.Tensor | None = None
     uid: int = 0
+    image_name: str = ""
 
 
 def train_view(W: int, H: int, R: np.ndarray, T: np.ndarray, device) -> TrainView:

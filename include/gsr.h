@@ -1170,6 +1170,39 @@ int gsr_image_metrics(gsr_alloc_fn scratch_alloc, void* scratch_ctx, int N, int 
                       int with_ssim, const float* render, const float* gt, uint8_t* render_bytes, uint8_t* gt_bytes,
                       double* out, void* stream);
 
+/*
+ * View preparation (the reference's loadCam -> PILtoTorch -> Camera.__init__):
+ * PIL.Image.resize's 8-bit bicubic resample, byte for byte, and the float
+ * planes of the resized bytes.  Byte images are [N,H,W,C], C = 1..4.
+ *
+ * gsr_resample_ksize: the taps of one window, ceil(2 max(in/out, 1)) * 2 + 1.
+ *
+ * gsr_resample_coeffs (host only, float64): Pillow's table of one axis for
+ * the bicubic filter (a = -0.5).  k [out_size][ksize] receives the weights
+ * normalised to sum 1 and rounded to 22 fractional bits (0 past a window's
+ * count), bounds [out_size][2] each window's (first input index, count).
+ *
+ * gsr_image_resample8: one pass along `axis` (1: W, 0: H) to `out_size`,
+ *   out byte = clip8((2^21 + sum in byte * k) >> 22)  in int32.
+ * `k` and `bounds` are DEVICE copies of that axis' table, k transposed to
+ * tap-major [ksize][out_size].  `in` and `out` must not overlap.  A resize
+ * is the pass along W, then the pass along H on its bytes; a pass that
+ * keeps its size is not run.  No atomics: an image's bytes do not depend on
+ * the batch.  Asynchronous on `stream`.
+ *
+ * gsr_view_planes: rgb [N,H,W,3] (and mask [N,H,W] or NULL) ->
+ *   original [N,3,H,W] = fl(byte / 255), an IEEE divide;
+ *   gray [N,1,H,W] = fl(fl(fl(0.299f r) + fl(0.587f g)) + fl(0.114f b));
+ *   gt_mask [N,1,H,W] = fl(mask byte / 255) (ignored when mask is NULL),
+ * one launch, asynchronous on `stream`.
+ */
+int gsr_resample_ksize(int in_size, int out_size);
+int gsr_resample_coeffs(int in_size, int out_size, int32_t* k, int32_t* bounds);
+int gsr_image_resample8(long long N, int H, int W, int C, int axis, int out_size, const uint8_t* in, uint8_t* out,
+                        const int32_t* k, const int32_t* bounds, void* stream);
+int gsr_view_planes(long long N, int H, int W, const uint8_t* rgb, const uint8_t* mask, float* original, float* gray,
+                    float* gt_mask, void* stream);
+
 /* Human-readable message for the last non-OK status on this thread. */
 const char* gsr_last_error(void);
 
