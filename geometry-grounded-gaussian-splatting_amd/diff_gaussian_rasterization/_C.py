@@ -357,6 +357,10 @@ def rasterize_gaussians_backward(background, means3D, colors, opacity, scales, r
     if rest is not None:
         outs["dsh_rest"] = alloc(*sh_rest.shape, **fopt)
         SHM = 1 + sh_rest.size(1)
+    if P == 0:  # (SHM and SGM read 0 above: an empty gradient still has its input's shape, [0, M, 3])
+        for k, t in (("dsh", sh), ("dsg_axis", sg_axis), ("dsg_sharpness", sg_sharpness), ("dsg_color", sg_color)):
+            if t is not None and t.dim() == outs[k].dim():
+                outs[k] = torch.zeros(t.shape, **fopt)
     if P != 0:
         a = {k: _dev_contig(v, k) for k, v in dict(
             background=background, means3D=means3D, colors=colors, opacity=opacity, scales=scales,
@@ -589,14 +593,9 @@ def view_color_grads_chunked(gathered, campos, n_views: int, chunk: int, means3D
     [P, SHM - 1, 3]."""
     P = means3D.shape[0]
     SHM = dL_dsh.shape[1] if dL_dsh_rest is None else 1 + dL_dsh_rest.shape[1]
-    SGM = dL_dsg_color.shape[1] if dL_dsg_color is not None and dL_dsg_color.numel() else 0
-    if gathered.numel() != n_views * P * 3 or campos.numel() != 4 * n_views or chunk < 1:
-        raise RuntimeError("gsr view_color_grads_chunked: `gathered` must hold n_views * 3 P floats, `campos` "
-                           "n_views * 4, chunk >= 1")
+    SGM = dL_dsg_color.shape[1] if dL_dsg_color is not None and dL_dsg_color.dim() == 3 else 0  # (P may be 0)
     want = {"means3D": (means3D, (P, 3)), "dL_dsh": (dL_dsh, (P, SHM, 3) if dL_dsh_rest is None else (P, 1, 3))}
     if dL_dsh_rest is not None:
-        if SHM < 2:
-            raise RuntimeError("gsr view_color_grads_chunked: the split SH layout needs SHM >= 2")
         want["dL_dsh_rest"] = (dL_dsh_rest, (P, SHM - 1, 3))
     if SGM:
         want.update(dL_dsg_axis=(dL_dsg_axis, (P, SGM, 3)), dL_dsg_sharpness=(dL_dsg_sharpness, (P, SGM)),
@@ -604,11 +603,22 @@ def view_color_grads_chunked(gathered, campos, n_views: int, chunk: int, means3D
     if sg_degree:
         want.update(sg_axis=(sg_axis, (P, SGM, 3)), sg_sharpness=(sg_sharpness, (P, SGM)),
                     sg_color=(sg_color, (P, SGM, 3)))
-    for name, (t, shape) in list(want.items()) + [("gathered", (gathered, tuple(gathered.shape))),
-                                                  ("campos", (campos, tuple(campos.shape)))]:
-        if tuple(t.shape) != shape or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError(f"gsr view_color_grads_chunked: `{name}` must be a contiguous fp32 HIP tensor "
-                               f"of shape {shape}")
+    # (the checks of view_color_grads below, in its order and with its messages)
+    for name, t in [("gathered", gathered), ("campos", campos)] + [(k, t) for k, (t, _) in want.items()]:
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"gsr view_color_grads_chunked: `{name}` must be a contiguous fp32 HIP tensor")
+    if gathered.numel() != n_views * P * 3 or campos.numel() != 4 * n_views or chunk < 1:
+        raise RuntimeError("gsr view_color_grads_chunked: `gathered` must hold n_views * 3 P floats, `campos` "
+                           "n_views * 4, chunk >= 1")
+    if dL_dsh_rest is not None and SHM < 2:
+        raise RuntimeError("gsr view_color_grads_chunked: the split SH layout needs SHM >= 2")
+    for name, (t, shape) in want.items():
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"gsr view_color_grads_chunked: `{name}` has shape {tuple(t.shape)}, "
+                               f"expected {shape}")
+    if not 0 <= int(sh_degree) <= 3 or SHM < (int(sh_degree) + 1) ** 2 or not 0 <= int(sg_degree) <= SGM:
+        raise RuntimeError(f"gsr view_color_grads_chunked: degrees (SH {sh_degree}, SG {sg_degree}) do not fit "
+                           f"{SHM} SH rows and {SGM} SG lobes")
     dev = means3D.device
     p = lambda t: _ptr(t) if t is not None and t.numel() else None  # noqa: E731
     call(dev, "gsr_view_color_grads_chunked", P, int(sh_degree), SHM, int(sg_degree), SGM, int(n_views), int(chunk),
@@ -624,7 +634,7 @@ def view_color_grads(gathered, n_views: int, means3D, sh_degree: int, dL_dsh, sg
     [n_views, P * 3 + 4] DC rows + camera centres; outputs written in place."""
     P = means3D.shape[0]
     SHM = dL_dsh.shape[1]
-    SGM = dL_dsg_color.shape[1] if dL_dsg_color is not None and dL_dsg_color.numel() else 0
+    SGM = dL_dsg_color.shape[1] if dL_dsg_color is not None and dL_dsg_color.dim() == 3 else 0  # (P may be 0)
     need = [(gathered, "gathered"), (means3D, "means3D"), (dL_dsh, "dL_dsh")]
     if SGM:
         need += [(dL_dsg_axis, "dL_dsg_axis"), (dL_dsg_sharpness, "dL_dsg_sharpness"), (dL_dsg_color, "dL_dsg_color")]

@@ -350,10 +350,14 @@ class OverlappedViewGrads:
         host memory behind an event and read at the next `begin()` (the next
         rasterizer backward) or by an explicit `check()` — no host
         synchronisation per backward, so the host keeps queueing the rest of
-        the backward and the optimizer step while the GPU works.  A training
-        loop that must never apply a step with a failed peer calls `check()`
-        before `optimizer.step()` (one wait on an event the GPU has long
-        passed by then, since the step's gradients are complete);
+        the backward and the optimizer step while the GPU works.  In this
+        mode a healthy rank's backward returns with NaN in the failed rank's
+        ranges, so `check()` before `optimizer.step()` is REQUIRED, not
+        optional (one wait on an event the GPU has long passed by then,
+        since the step's gradients are complete).  `uninstall()` and leaving
+        the `with` block call `check()` as well, so a failure in the last
+        backward is raised there; a block that is already unwinding another
+        exception keeps that exception and drops the pending flag;
       * True (the default for host tensors, where the read costs nothing):
         `finish()` reads the flag and raises in the same backward, at the
         price of one host synchronisation per backward after its last
@@ -396,15 +400,24 @@ class OverlappedViewGrads:
         return self
 
     def uninstall(self) -> None:
+        """Remove the hook, then raise the last backward's pending failure
+        flag (`check()`): no later `begin()` would read it."""
         import diff_gaussian_rasterization as dgr
         if dgr._view_exchange is self:
             dgr.set_view_exchange(None)
+        self.check()
 
     def __enter__(self):
         return self.install()
 
-    def __exit__(self, *exc):
-        self.uninstall()
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.uninstall()
+            return
+        try:  # the block is unwinding its own exception: a pending flag must not mask it
+            self.uninstall()
+        except Exception:  # noqa: BLE001 - the body's exception is the one to raise
+            pass
 
     # ---- the rasterizer backward's protocol ---------------------------
     def dc_rows(self, P: int, device) -> torch.Tensor:

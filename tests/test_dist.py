@@ -276,7 +276,7 @@ def _overlap_grads(P, seed):
             torch.zeros(P, 0, 3), torch.zeros(P, 0), torch.zeros(P, 0, 3), r(P, 3), r(P, 4))
 
 
-def _error_worker(rank, world, port, outdir, sync_check=None):
+def _error_worker(rank, world, port, outdir, sync_check=None, at_exit=False):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "geometry-grounded-gaussian-splatting_amd"), HERE]
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -294,20 +294,32 @@ def _error_worker(rank, world, port, outdir, sync_check=None):
     ex.chunk_size = lambda P_: 8
     grads = _overlap_grads(P, seed=rank)
     mine = [t.clone() for t in grads]
-    ex.begin(torch.zeros(3), P, True, True)
-    ex.dc_rows(P, "cpu").copy_(torch.arange(3 * P, dtype=torch.float32) * (rank + 1))
-    cb = ex.hook(grads)
-    for b in range(0, P, 8):  # as gsr_rasterize_backward_ex calls its callback: every range, after a failure too
-        cb(b, min(P, b + 8))
-    raised = None
-    try:
+
+    def backward():
+        ex.begin(torch.zeros(3), P, True, True)
+        ex.dc_rows(P, "cpu").copy_(torch.arange(3 * P, dtype=torch.float32) * (rank + 1))
+        cb = ex.hook(grads)
+        for b in range(0, P, 8):  # as gsr_rasterize_backward_ex calls its callback: every range, after a failure too
+            cb(b, min(P, b + 8))
         ex.settle(True)
         ex.finish(grads, torch.randn(P, 3), None, None, None, 3, 0)
+
+    raised, returned = None, False
+    try:
+        if at_exit:  # the failing backward is the last one inside the `with` block: leaving it reads the flag
+            with ex:
+                backward()
+                returned = True
+        else:
+            backward()
     except (ValueError, RuntimeError) as e:
         raised = str(e)
     out = {"raised": raised, "works_left": len(ex._works), "active": ex._active,
            "means3D": grads[3], "mine": mine[3]}
-    if sync_check is False:  # deferred: the flag is read by the next begin() (or check()), before any collective
+    if at_exit:
+        import diff_gaussian_rasterization as dgr
+        out.update(returned=returned, pending=ex._pending is not None, installed=dgr._view_exchange is not None)
+    elif sync_check is False:  # deferred: the flag is read by the next begin() (or check()), before any collective
         out["raised_in_backward"] = raised
         try:
             ex.begin(torch.zeros(3), P, True, True)
@@ -332,23 +344,32 @@ def _error_worker(rank, world, port, outdir, sync_check=None):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("sync_check", [None, False])
-def test_overlapped_exchange_failure_keeps_ranks_in_lockstep(tmp_path, sync_check):
+@pytest.mark.parametrize("sync_check,at_exit", [(None, False), (False, False), (False, True)],
+                         ids=["None", "False", "False-at_exit"])
+def test_overlapped_exchange_failure_keeps_ranks_in_lockstep(tmp_path, sync_check, at_exit):
     """A range whose exchange raises on one rank: that rank still
     posts every remaining range's collectives — on NaN rows — waits for all of
     its works and re-raises; the peer's backward completes its collectives (no
     deadlock) and then raises too (the failure flag all-reduced at
     the end of every backward), so no rank hands NaN-summed gradients to its
-    optimizer; the next step runs normally on both."""
+    optimizer; the next step runs normally on both.  `at_exit`:
+    the failing backward is the last one inside `with OverlappedViewGrads(
+    sync_check=False)` — the healthy peer's backward returns and leaving the
+    block raises the peer's failure; the failing rank's own error leaves its
+    block unmasked by the flag it deferred for itself."""
     port = _free_port()
-    mp.start_processes(_error_worker, args=(2, port, str(tmp_path), sync_check), nprocs=2, join=True,
+    mp.start_processes(_error_worker, args=(2, port, str(tmp_path), sync_check, at_exit), nprocs=2, join=True,
                        start_method="spawn")
     e0 = torch.load(tmp_path / "e0.pt", weights_only=True)
     e1 = torch.load(tmp_path / "e1.pt", weights_only=True)
     assert e0["raised"] == "injected failure in range [8, 16)"
     assert e1["raised"] is not None and "a peer rank's rasterizer backward failed" in e1["raised"]
     assert e0["works_left"] == 0 and not e0["active"] and not e1["active"]
-    if sync_check is False:  # deferred (ADVICE r5): the peer's backward returns; its next begin() raises
+    if at_exit:  # the peer's backward returned, leaving the block raised; no flag or hook is left behind
+        assert e1["returned"] and not e0["returned"]
+        for e in (e0, e1):
+            assert not e["pending"] and not e["installed"]
+    elif sync_check is False:  # deferred (ADVICE r5): the peer's backward returns; its next begin() raises
         assert e1["raised_in_backward"] is None and not e1["active_after_begin"]
     m1 = e1["means3D"]
     torch.testing.assert_close(m1[:8], e0["mine"][:8] + e1["mine"][:8])  # posted before the failure: summed

@@ -247,6 +247,132 @@ def test_overlapped_exchange_one_rank_matches_plain_backward(tmp_path, sg_degree
         assert err <= 1e-5, (k, err)
 
 
+@pytest.mark.parametrize("P,chunks", [(513, 2), (513, 3), (512, 2), (100, 4), (257, 1), (0, 3)])
+def test_overlapped_exchange_ranges_at_their_edges(tmp_path, P, chunks):
+    """The whole backward through OverlappedViewGrads (one-rank RCCL group,
+    64x48, SH 3 + SG 7) where the Gaussian ranges end: the library's range
+    size (gsr_backward_chunk_size: the Gaussians per chunk rounded up to 256)
+    gives ranges of 512 / 1 (513, 2), 256 / 256 / 1 (513, 3), 256 / 256
+    (512, 2), 100 (100, 4: the range longer than P) and 257 (257, 1); P = 0
+    completes with empty gradients.
+
+    The colour rows are checked per element, not by norm.
+    (1) The DC rows against the plain backward's, |over - plain| <= 24 * 2^-24
+    * M per element.  Two backwards' DC rows can differ only by the order of
+    the raster backward's atomics: one wave per 16x16 tile sums its pixels in
+    a fixed order and issues one atomic add per Gaussian, so a Gaussian's
+    dL/dcolour is a sum of at most T = 12 tile partials (64x48) in an order
+    that may change.  Either order is within (T - 1) u M of the exact sum, M
+    = sum over the pixels of |term|, so the two differ by at most 22 u M; the
+    product with SH_C0 adds its own rounding (2 u M at most).  M is taken
+    from the plain backward itself: its DC row for the upstream colour
+    gradient in absolute value (dL/dcolour is linear in it with non-negative
+    weights alpha T, and the clamp mask is the forward's).  A DC row in the
+    wrong slot (dc_rows, the gathered offset, the kernel's range arithmetic)
+    misses this by orders of magnitude.
+    (2) Every other colour row against the plain backward's, within
+    bar(S of the plain DC rows) + S(the bound of (1)): every row is linear
+    in the DC row and S is homogeneous in |DC row|, so (1)'s allowance
+    reaches a row as at most S evaluated on it.
+    (3) Every colour row against viewgrads_ref.rebuild(float64) of the
+    overlapped backward's own DC rows (with one rank a one-view sum), within
+    viewgrads_ref.bar: the rebuild alone, without the atomics' allowance.
+    Geometry gradients: rel. L2 <= 1e-5, as the test above."""
+    import math
+
+    import numpy as np
+
+    import gsr_scene as S
+    import helpers as Hh
+    import viewgrads_ref as VR
+    from diff_gaussian_rasterization import _C, GaussianRasterizationSettings, GaussianRasterizer
+    from gsr_dist import OverlappedViewGrads
+
+    dev = torch.device("cuda", 0)
+    W, H, sg_degree = 64, 48, 7
+    raw = S.make_gaussians(max(P, 1), sg_degree=sg_degree, seed=11, aspect=H / W, z_range=(2.0, 6.0))
+    inp = {k: v.detach()[:P].contiguous().to(dev) for k, v in S.activated_inputs(raw).items()}
+    cam = S.make_camera(W, H).to(dev)
+    settings = GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=math.tan(cam.FoVx / 2), tanfovy=math.tan(cam.FoVy / 2),
+        kernel_size=0.0, bg=torch.zeros(3, device=dev), scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+        projmatrix=cam.full_proj_transform, sh_degree=3, sg_degree=sg_degree, campos=cam.camera_center,
+        prefiltered=False, require_depth=True, debug=False)
+    g = {k: v.to(dev) for k, v in S.upstream_grads(H, W, seed=4).items()}
+
+    def step(colour_magnitude=False):
+        ps = {k: t.clone().requires_grad_(True) for k, t in inp.items()}
+        color, radii, mdepth, alpha, normal = GaussianRasterizer(settings)(
+            means3D=ps["means3D"], means2D=torch.zeros(P, 3, device=dev, requires_grad=True),
+            opacities=ps["opacities"], shs=ps["shs"], sg_axis=ps["sg_axis"], sg_sharpness=ps["sg_sharpness"],
+            sg_color=ps["sg_color"], scales=ps["scales"], rotations=ps["rotations"])
+        if colour_magnitude:  # (the colour image's upstream gradient in absolute value, nothing else)
+            torch.autograd.backward([color], [g["color"].abs()])
+        else:
+            torch.autograd.backward([color, mdepth, normal], [g["color"], g["mdepth"], g["normal"]])
+        torch.cuda.synchronize()
+        return {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in ps.items()}
+
+    plain = step()
+    magnitude = step(colour_magnitude=True)["shs"][:, 0, :] if P else None
+    store = dist.FileStore(str(tmp_path / "store"), 1)
+    dist.init_process_group("nccl", store=store, rank=0, world_size=1, device_id=dev)
+    try:
+        with OverlappedViewGrads(chunks=chunks) as ex:
+            over = step()
+            ex.check()
+    finally:
+        dist.destroy_process_group()
+    for k in plain:
+        assert over[k].shape == plain[k].shape == inp[k].shape, k
+    if P == 0:
+        return
+    cs = _C.backward_chunk_size(P, chunks)
+    print(f"ranges of {cs}: " + " / ".join(str(min(P, b + cs) - b) for b in range(0, P, cs)))
+    colour = {"sh": "shs", "sg_axis": "sg_axis", "sg_sharpness": "sg_sharpness", "sg_color": "sg_color"}
+    for k in plain:
+        if k in colour.values():
+            continue
+        want, got = plain[k].double(), over[k].double()
+        assert bool(torch.isfinite(got).all()), k
+        err = float((got - want).norm() / want.norm().clamp_min(1e-30))
+        assert err <= 1e-5, (k, err)
+    n64 = lambda t: t.detach().cpu().numpy().astype(np.float64)  # noqa: E731
+    sg = [inp[k].cpu().numpy() for k in ("sg_axis", "sg_sharpness", "sg_color")]
+    means, campos = inp["means3D"].cpu().numpy(), cam.camera_center.reshape(1, 3).cpu().numpy()
+    dc_over, dc_plain = n64(over["shs"][:, 0, :]), n64(plain["shs"][:, 0, :])
+    assert dc_plain.any()  # (the view sees the scene)
+    # (1) the DC rows against the plain backward's, per element
+    M = n64(magnitude)
+    assert np.all(M >= 0.0) and np.all(np.abs(dc_plain) <= (1.0 + 1e-4) * M + 1e-30)  # (M is a magnitude of it)
+    dc_bound = 24.0 * VR.U * M + 1e-30
+    dc_err = np.abs(dc_over - dc_plain)
+    bad = ~(dc_err <= dc_bound)
+    live = M > 0.0
+    print(f"{int((dc_over != dc_plain).any(1).sum())} of {P} DC rows differ between the two backwards; worst "
+          f"{float((dc_err[live] / (VR.U * M[live])).max()):.2f} u M against 24")
+    assert not bad.any(), ("DC rows against the plain backward", np.argwhere(bad)[:4].tolist())
+    fields = {"dc": (float((dc_err[live] / (VR.U * M[live])).max()), 24.0)}
+    ref, S_over = VR.rebuild(dc_over[None], campos, means, 3, 16, sg_degree, sg_degree, *sg)
+    _, S_plain = VR.rebuild(dc_plain[None], campos, means, 3, 16, sg_degree, sg_degree, *sg)
+    _, S_noise = VR.rebuild(dc_bound[None], campos, means, 3, 16, sg_degree, sg_degree, *sg)
+    for kind, k in colour.items():
+        got = n64(over[k])
+        # (2) against the plain backward's rows
+        err = np.abs(got - n64(plain[k]))
+        bad = ~(err <= VR.bar(kind, S_plain[kind]) + (1.0 + 1e-6) * S_noise[kind])
+        assert not bad.any(), (kind, "against the plain backward", np.argwhere(bad)[:4].tolist())
+        # (3) against the rebuild of its own DC rows
+        err = np.abs(got - ref[kind])
+        bad = ~(err <= VR.bar(kind, S_over[kind]))
+        assert not bad.any(), (kind, "against the rebuild of its own DC rows", np.argwhere(bad)[:4].tolist())
+        live = S_over[kind] > 0.0
+        assert live.any(), kind
+        fields[kind] = (float((err[live] / (VR.U * S_over[kind][live])).max()), 4 * VR.C_KIND[kind])
+    Hh.record_margins(fields, f"P {P}, {chunks} chunks: DC rows against the plain backward's (u M), the other "
+                              "rows against the rebuild of their own DC rows (u S)")
+
+
 # ---- two ranks through the real HIP backward (one GPU shared, gloo) ----
 def _two_rank_worker(rank, world, port, outdir, sg_degree):
     import math
@@ -327,6 +453,148 @@ def test_two_ranks_exchange_sums_views_on_gpu(tmp_path, sg_degree):
             assert bool(torch.isfinite(a).all()), (form, k)
             err = float((a.double() - want).norm() / want.norm().clamp_min(1e-30))
             assert err <= 1e-5, (form, k, err)
+
+
+# ---- the deferred failure flag on device tensors ----
+def _deferred_flag_worker(rank, world, port, outdir):
+    import math
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    sys.path[:0] = [root, os.path.join(root, "geometry-grounded-gaussian-splatting_amd"), here]
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    import diff_gaussian_rasterization as dgr
+    import gsr_scene as S
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+    from gsr_dist import OverlappedViewGrads
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    P, W, H, chunks = 600, 64, 48, 3
+    assert dgr._C.backward_chunk_size(P, chunks) == 256  # ranges [0, 256), [256, 512), [512, 600)
+    raw = S.make_gaussians(P, seed=7, aspect=H / W, z_range=(2.0, 6.0))
+    inp = {k: v.detach().contiguous().to(dev) for k, v in S.activated_inputs(raw).items()}
+    cam = S.orbit_cameras(2, W, H, center_z=4.0, max_deg=8.0)[rank].to(dev)
+    settings = GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=math.tan(cam.FoVx / 2), tanfovy=math.tan(cam.FoVy / 2),
+        kernel_size=0.0, bg=torch.zeros(3, device=dev), scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+        projmatrix=cam.full_proj_transform, sh_degree=3, sg_degree=0, campos=cam.camera_center,
+        prefiltered=False, require_depth=True, debug=False)
+    g = {k: v.to(dev) for k, v in S.upstream_grads(H, W, seed=4 + rank).items()}
+
+    def step():
+        ps = {k: t.clone().requires_grad_(True) for k, t in inp.items()}
+        color, radii, mdepth, alpha, normal = GaussianRasterizer(settings)(
+            means3D=ps["means3D"], means2D=torch.zeros(P, 3, device=dev, requires_grad=True),
+            opacities=ps["opacities"], shs=ps["shs"], sg_axis=ps["sg_axis"], sg_sharpness=ps["sg_sharpness"],
+            sg_color=ps["sg_color"], scales=ps["scales"], rotations=ps["rotations"])
+        torch.autograd.backward([color, mdepth, normal], [g["color"], g["mdepth"], g["normal"]])
+        torch.cuda.synchronize()
+        return {k: t.grad.cpu() for k, t in ps.items() if t.grad is not None and t.numel()}
+
+    class Failing(OverlappedViewGrads):
+        """A host-side Python exception in rank 0's second range (as `Failing` in tests/test_dist.py): held by
+        hook(), re-raised by settle(); nothing on the GPU faults, the NaN rows are ordinary data."""
+        fail = True
+
+        def on_chunk(self, b, e, grads):
+            if self.fail and rank == 0 and b == 256:
+                raise ValueError("injected failure in range [256, 512)")
+            super().on_chunk(b, e, grads)
+
+    def attempt(fn):
+        try:
+            return fn(), None
+        except (ValueError, RuntimeError) as e:  # noqa: PERF203
+            return None, str(e)
+
+    out = {"plain": step()}
+    # 1: the failing backward, then check()
+    ex = Failing(chunks=chunks).install()  # (sync_check left at its default: deferred on device tensors)
+    out["s1_grads"], out["s1_backward"] = attempt(step)
+    pend = ex._pending
+    out["s1_pending"] = (pend is not None and pend[0].is_pinned() and not pend[0].is_cuda
+                         and isinstance(pend[1], torch.cuda.Event))
+    _, out["s1_check"] = attempt(ex.check)
+    out["s1_pending_after"] = ex._pending is not None
+    # 2: the failing backward and no check(): the next backward's begin() raises, on every rank, before any
+    # collective is posted
+    _, out["s2_backward"] = attempt(step)
+    ex.fail = False
+    _, out["s2_next_backward"] = attempt(step)
+    out["s2_active"] = ex._active
+    _, out["s2_uninstall"] = attempt(ex.uninstall)  # (the flag was read by begin(): nothing is pending)
+    # 3: the failing backward is the last one inside a `with` block: leaving it raises on the healthy rank, and
+    # rank 0's own error leaves its block unmasked
+
+    def in_block():
+        with Failing(chunks=chunks):
+            step()
+            out["s3_body_finished"] = True
+
+    out["s3_body_finished"] = False
+    _, out["s3_block"] = attempt(in_block)
+    out["s3_installed"] = dgr._view_exchange is not None
+    # afterwards the group is still in lockstep: one more backward on both ranks
+    with OverlappedViewGrads(chunks=chunks) as ex4:
+        out["after"] = step()
+        ex4.check()
+    torch.save(out, os.path.join(outdir, f"d{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+def test_deferred_failure_flag_on_device_tensors(tmp_path):
+    """the GPU branch of OverlappedViewGrads' deferred failure flag
+    (a pinned non-blocking copy of the all-reduced flag behind an event).  Two
+    ranks share cuda:0 over gloo, P = 600 in three ranges of 256, 64x48;
+    rank 0's exchange raises a ValueError in its second range.  Rank 0's
+    backward raises it; rank 1's backward returns with the first range summed
+    over the two views and the later ranges NaN, holding a pinned flag and an
+    event; then the failure is raised on rank 1 by check(), or (no check) by
+    the next backward's begin() on both ranks, or by leaving the `with`
+    block; and one more backward on both ranks gives the two-view sum."""
+    import torch.multiprocessing as mp
+
+    import helpers as Hh
+    port = Hh.free_port()
+    mp.start_processes(_deferred_flag_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True,
+                       start_method="spawn")
+    r0, r1 = (torch.load(tmp_path / f"d{k}.pt", weights_only=True) for k in range(2))
+    injected, peer = "injected failure in range [256, 512)", "a peer rank's rasterizer backward failed"
+    # 1
+    assert r0["s1_backward"] == injected and r0["s1_grads"] is None
+    assert r1["s1_backward"] is None and r1["s1_pending"]
+    assert r1["s1_check"] is not None and peer in r1["s1_check"]
+    assert r0["s1_check"] is not None and peer in r0["s1_check"]  # (rank 0 defers the flag for itself too)
+    assert not r0["s1_pending_after"] and not r1["s1_pending_after"]
+    for k in ("means3D", "opacities", "scales", "rotations"):
+        got = r1["s1_grads"][k].double()
+        want = r0["plain"][k].double() + r1["plain"][k].double()
+        err = float((got[:256] - want[:256]).norm() / want[:256].norm().clamp_min(1e-30))
+        assert err <= 1e-5, (k, err)  # the first range: posted before the failure, the two views' sum
+        assert bool(torch.isnan(got[256:]).all()), k  # the failed rank's later ranges: NaN, not one view alone
+    assert float(r0["plain"]["means3D"][:256].abs().sum()) > 0 and float(r1["plain"]["means3D"][256:].abs().sum()) > 0
+    # 2
+    assert r0["s2_backward"] == injected and r1["s2_backward"] is None
+    for r in (r0, r1):
+        assert r["s2_next_backward"] is not None and peer in r["s2_next_backward"]
+        assert not r["s2_active"] and r["s2_uninstall"] is None
+    # 3
+    assert r0["s3_block"] == injected and not r0["s3_body_finished"]
+    assert r1["s3_body_finished"] and r1["s3_block"] is not None and peer in r1["s3_block"]
+    assert not r0["s3_installed"] and not r1["s3_installed"]
+    # afterwards
+    for k, p0 in r0["plain"].items():
+        want = p0.double() + r1["plain"][k].double()
+        a, b = r0["after"][k], r1["after"][k]
+        assert torch.equal(a, b), k
+        assert bool(torch.isfinite(a).all()), k
+        err = float((a.double() - want).norm() / want.norm().clamp_min(1e-30))
+        assert err <= 1e-5, (k, err)
 
 
 # ---- C4 / C5 at their full workload: N ranks sharing cuda:0 (gloo) ----
