@@ -49,7 +49,10 @@ struct SelectState {
 };
 
 // rank = q (n - 1) in fp32, below / above = floor / ceil, as ATen's quantile
+// (rank and weight are two tensor operations there, each rounded: contracted into one fma, rank - floor
+// keeps the product's unrounded tail, up to half an ulp of the rank, and Q moves by that times b - a)
 __global__ void select_init_kernel(SelectState* st, long long n, const float* q_in, long long P_ratio) {
+#pragma clang fp contract(off)
     float q;
     if (q_in)
         q = *q_in;

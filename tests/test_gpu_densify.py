@@ -25,11 +25,11 @@ import torch
 import densify_ref as R
 import gsr_densify
 import gsr_optim
+from densify_cases import U, filter64, filter_random_case, layout, margin_ok, random_case, rows64  # noqa: F401
 from test_densify import CASES, Cam, cams_of, case, model_of
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-U = 2.0 ** -24
 _RATIOS: dict = {}
 
 
@@ -43,51 +43,6 @@ def hip_model(c, **kw):
 
 def scalars(c):
     return tuple(float(x) for x in c["scalars"])
-
-
-def layout(c):
-    """Final rows (source, own noise row, the parent clone's noise row) of a golden case, derived
-    from its inputs alone (the fixture's tie margin makes the decisions arithmetic-independent)."""
-    max_grad, min_opacity, extent = scalars(c)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        gr = np.nan_to_num(c["accum"] / c["denom"], nan=0.0)
-        ga = np.nan_to_num(c["accum_abs"] / c["denom"], nan=0.0)
-    big = np.exp(c["in_scaling"].astype(np.float64)).max(axis=1) > 0.01 * extent
-    low = 1 / (1 + np.exp(-c["in_opacity"][:, 0].astype(np.float64))) < min_opacity
-    hi = gr >= np.float32(max_grad)
-    clone, split, cs = hi & ~big, (hi & big) | (ga >= c["Q"]), bool(0.0 >= c["Q"])
-    crank, srank = np.cumsum(clone) - clone, np.cumsum(split) - split
-    C, So = int(clone.sum()), int(split.sum())
-    S = So + (C if cs else 0)
-    idx = np.arange(len(gr))
-    rows = [(i, -1, -1) for i in idx[~split & ~low]]
-    rows += [(i, crank[i], -1) for i in idx[clone & ~low]] if not cs else []
-    for j in range(2):
-        rows += [(i, C + j * S + srank[i], -1) for i in idx[split & ~low]]
-        if cs:
-            rows += [(i, C + j * S + So + crank[i], crank[i]) for i in idx[clone & ~low]]
-    return np.array(rows, np.int64).reshape(-1, 3), C, S
-
-
-def rows64(c, rows, C):
-    """float64 new positions and scalings of `rows`, with the two bounds."""
-    Rm = R.rotation_matrices(torch.tensor(c["in_rotation"]).double()).numpy()
-    s = c["in_scaling"].astype(np.float64)
-    xyz, eps = c["in_xyz"].astype(np.float64), c["noise"].astype(np.float64)
-    src, own, par = rows[:, 0], rows[:, 1], rows[:, 2]
-    new = own >= 0
-    base = xyz[src].copy()
-    hp = par >= 0
-    base[hp] += np.einsum("nij,nj->ni", Rm[src[hp]], np.exp(s[src[hp]]) * eps[par[hp]])
-    v = np.zeros_like(base)
-    v[new] = np.exp(s[src[new]]) * eps[own[new]]
-    pos = base + np.einsum("nij,nj->ni", Rm[src], v)
-    pos_bound = 16 * U * (np.abs(base) + np.einsum("nij,nj->ni", np.abs(Rm[src]), np.abs(v)))
-    child = own >= C
-    sc = s[src].copy()
-    sc[child] = np.log(np.exp(sc[child]) / 1.6)
-    sc_bound = 8 * U * np.maximum(1.0, np.minimum(np.abs(sc), np.abs(s[src])))
-    return pos, pos_bound, sc, sc_bound, new, child
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -138,32 +93,6 @@ def parity_ratios():
 
 
 # ------------------------------------------------------------------ edge cases
-def random_case(P, seed, sg=True, low_all_but_one=False):
-    """Inputs whose decisions sit far from every threshold (values from well-separated sets)."""
-    rng = np.random.default_rng(seed)
-    max_grad, min_opacity, extent = 0.0002, 0.05, 4.0
-    nsg = 1 if sg else 0
-    op = rng.standard_normal((P, 1)) * 2.0
-    thr = math.log(min_opacity / (1 - min_opacity))
-    op[np.abs(op - thr) < 0.05] += 0.2
-    if low_all_but_one:
-        op[:] = -6.0
-        op[P // 2] = 1.0
-    sc = np.log(0.01 * extent * rng.choice([0.2, 0.5, 0.8, 1.5, 3.0], (P, 3))) - rng.random((P, 3)) * 0.1
-    params = dict(xyz=rng.standard_normal((P, 3)) * 2, f_dc=rng.standard_normal((P, 1, 3)),
-                  f_rest=rng.standard_normal((P, 3, 3)) * 0.1, opacity=op, scaling=sc,
-                  rotation=rng.standard_normal((P, 4)), sg_axis=rng.standard_normal((P, nsg, 3)),
-                  sg_sharpness=rng.standard_normal((P, nsg)), sg_color=rng.standard_normal((P, nsg, 3)))
-    params = {k: v.astype(np.float32) for k, v in params.items()}
-    denom = rng.integers(0, 20, P).astype(np.float32)
-    accum = (max_grad * rng.choice([0.3, 0.7, 1.5, 3.0], P) * denom).astype(np.float32)
-    accum_abs = (np.exp(rng.standard_normal(P)) * max_grad * 2 * denom * (rng.random(P) < 0.7)).astype(np.float32)
-    moments = {n: ((rng.standard_normal(v.shape) * 0.01).astype(np.float32),
-                   (rng.random(v.shape) * 1e-4).astype(np.float32)) for n, v in params.items()}
-    noise = torch.randn((5 * P, 3), generator=torch.Generator().manual_seed(seed))
-    return params, (accum, accum_abs, denom), moments, noise, (max_grad, min_opacity, extent)
-
-
 def build(params, stats, moments, optimizer_cls):
     g = R.RefGaussians(params, device=DEV, optimizer_cls=optimizer_cls)
     if moments is not None:
@@ -294,62 +223,10 @@ def test_radix_select_beyond_torch_quantile_limit():
 
 
 # ------------------------------------------------------------------- 3D filter
-def filter64(xyz, cams):
-    """float64 filter, the seen mask and the issue's bound 4 u (sum|x_i R_i2| + |T_2|) sqrt(0.2) / F."""
-    x = xyz.astype(np.float64)
-    dist = np.full(len(x), np.inf)
-    M = np.zeros(len(x))
-    F = max(c.Fx for c in cams)
-    for c in cams:
-        Rm, T = c.R.double().numpy(), c.T.double().numpy()
-        pc = x @ Rm + T
-        z = pc[:, 2]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ok = (z > 0.2) & (np.abs(pc[:, 0] / z) <= c.image_width / c.Fx * 0.575) & \
-                 (np.abs(pc[:, 1] / z) <= c.image_height / c.Fy * 0.575)
-        better = ok & (z < dist)
-        dist[better] = z[better]
-        M[better] = (np.abs(x) @ np.abs(Rm[:, 2]) + abs(T[2]))[better]
-    seen = np.isfinite(dist)
-    far = np.argmax(np.where(seen, dist, -np.inf))
-    dist[~seen], M[~seen] = dist[far], M[far]
-    return dist / F * math.sqrt(0.2), seen, 4 * U * M * math.sqrt(0.2) / F
-
-
-def margin_ok(xyz, cams, m=1e-5):
-    """Points within the tie margin of z = 0.2 or a frustum bound of any camera."""
-    x = xyz.astype(np.float64)
-    bad = np.zeros(len(x), bool)
-    for c in cams:
-        pc = x @ c.R.double().numpy() + c.T.double().numpy()
-        z = pc[:, 2]
-        bad |= np.abs(z - 0.2) <= m * 0.2
-        for k, b in ((0, c.image_width / c.Fx * 0.575), (1, c.image_height / c.Fy * 0.575)):
-            bad |= (z > 0.1) & (np.abs(np.abs(pc[:, k] / z) - b) <= m * b)
-    return bad
-
-
 @pytest.mark.parametrize("P", [1, 65, 1000])
 @pytest.mark.parametrize("n_cam", [1, 3, 130])
 def test_filter_3d(P, n_cam):
-    rng = np.random.default_rng(1000 * P + n_cam)
-    cams = []
-    for k in range(n_cam):
-        th = rng.uniform(-0.6, 0.6)
-        Rm = np.array([[math.cos(th), 0, math.sin(th)], [0, 1, 0], [-math.sin(th), 0, math.cos(th)]], np.float32)
-        F = float(rng.uniform(50, 80))
-        cams.append(Cam(Rm, (rng.standard_normal(3) * 0.2).astype(np.float32), (64, 48, F, F * 1.02)))
-    xyz = (rng.standard_normal((P, 3)) * np.array([1.5, 1.0, 1.0])).astype(np.float32)
-    xyz[:, 2] = rng.uniform(0.5, 6.0, P)
-    if P > 1:
-        xyz[P // 2] = (0.0, 0.0, -5.0)  # behind every camera
-    else:
-        xyz[0] = (0.05, -0.02, 3.0)
-    for _ in range(50):  # the tie margin: move the few points that sit on a threshold
-        bad = margin_ok(xyz, cams)
-        if not bad.any():
-            break
-        xyz[bad] += (rng.standard_normal((int(bad.sum()), 3)) * 1e-2).astype(np.float32)
+    xyz, cams = filter_random_case(P, n_cam)
     assert not margin_ok(xyz, cams).any()
     want, seen, bound = filter64(xyz, cams)
     assert seen.any() and (P == 1 or not seen[P // 2])
