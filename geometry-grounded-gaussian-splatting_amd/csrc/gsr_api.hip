@@ -10,8 +10,16 @@
 // and size the binning buffer, like the reference's cudaMemcpy at
 // rasterizer_impl.cu:384.  No other host<->device traffic, no device
 // allocation (all scratch comes from the caller's allocation callbacks).
+//
+// The render forward (gsr_rasterize_forward_ex2) and the point queries
+// (point_query_forward) share the Gaussian side of a forward, which exists
+// once: the geometry and binning carves (carve_alloc_scratch of
+// gsr_api_common.h on carve_geom / carve_binning), count_instances
+// (preprocess, prefiltered check, K) and build_tile_lists.  Each older public
+// entry point forwards to its implementation in one call.
 #include <stdio.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -51,12 +59,6 @@ uint32_t higher_msb(uint32_t n) {
     return msb;
 }
 
-// Binning path: the tile lists of tilelists.hip where the grid allows, else
-// the instance sort of binning.hip.
-int bin_path(uint32_t gx, uint32_t gy) {
-    return list_binning(gx, gy) ? kBinLists : kBinInstanceSort;
-}
-
 // `tmp`: where the forward-only scratch (scan / depth-sort temporaries) goes; NULL keeps it at the end of the buffer itself.  The
 // fields the backward reads come first either way, so it re-carves without
 // knowing which layout the forward used.
@@ -86,20 +88,19 @@ size_t carve_geom(void* base, int P, uint32_t gx, uint32_t gy, GeomState& g, Car
 
 // Binning buffer.  The point list comes first, so its offset depends only on
 // the base (gsr_debug_binning carves it knowing K alone); the rest depends
-// on the path: tile lists (tilelists.hip) or emit + tile-id sort.
+// on the binning path, `lists`: the tile lists of tilelists.hip where the
+// grid allows (list_binning), else emit + tile-id sort (binning.hip).
 // `tmp` as in carve_geom: the list-building (or key-sort) scratch, dead once
 // the point list is written, goes there instead of into the saved buffer.
-size_t carve_binning(void* base, int K, int P, uint32_t gx, uint32_t gy, int path, BinningState& b,
+size_t carve_binning(void* base, int K, int P, uint32_t gx, uint32_t gy, bool lists, BinningState& b,
                      Carver* tmp = nullptr) {
     Carver c(base);
     Carver& t = tmp ? *tmp : c;
     b.point_list = c.take<uint32_t>(K);
     const int tiles = (int)(gx * gy);
     const int tile_bits = (int)higher_msb((uint32_t)tiles);
-    b.path = path;
-    b.use_lists = path == kBinLists;
     b.key_bytes = tile_key_bytes(tile_bits);
-    if (b.use_lists) {
+    if (lists) {
         b.lists = list_layout(P, K, gx, gy);
         b.rows = t.take<uint2>(K);
         b.qrec = t.take<uint4>((size_t)2 * P);
@@ -147,6 +148,17 @@ size_t carve_bwd(void* base, int P, BwdState& s, int T = 0) {
     s.acc_abs = c.take<float>(P);
     s.tile_order = c.take<uint32_t>(T);
     return c.off;
+}
+
+// The backwards' accumulator block from the caller's callback: carve_bwd at `wb`, the aligned base of
+// `wbytes` + 256 bytes.
+int alloc_bwd(gsr_alloc_fn alloc, void* ctx, int P, int T, BwdState& s, void*& wb, size_t& wbytes) {
+    wbytes = carve_bwd(nullptr, P, s, T);
+    void* wbuf = alloc(ctx, wbytes + 256);
+    if (!wbuf) return fail(GSR_ERR_ALLOC, "backward buffer allocation failed");
+    wb = aligned_base(wbuf);
+    carve_bwd(wb, P, s, T);
+    return GSR_OK;
 }
 
 // sample_depth buffers (the reference's pointBuffer, point_binningBuffer,
@@ -297,6 +309,100 @@ struct StageTimer {
         GSR_TRY(expr, what);                                  \
     } while (0)
 
+// ---- the Gaussian side of a forward (render and point queries) ------------
+// CR/auxiliary.h:146-148 (the reference traps the kernel)
+const char* kPrefilteredMsg = "Point is filtered although prefiltered is set. This shouldn't happen!";
+
+// Words a caller has read back along with K (the point queries' totals; the
+// render forward leaves it empty): `words` (at most 4) from the device
+// address `src` into the host array `dst`.
+struct ReadWords {
+    const uint32_t* src = nullptr;
+    int words = 0;
+    uint32_t* dst = nullptr;
+};
+
+// Preprocess, the `prefiltered` near-plane check and the instance counts.
+// Ks.x = K, the reference's instance count (rect tiles): returned as
+// num_rendered and the capacity of the binning buffer.  Ks.y = K_live, the
+// instances that survive tile culling, which only the instance-sort path
+// needs and counts.  `queue_more` queues the caller's own launches whose
+// results `more` reads back (both behind the preprocess, before the one host
+// wait); it returns GSR_OK or the error it has reported.
+template <class Queue>
+int count_instances(const FwdParams& p, const GeomState& gs, int* radii, int prefiltered, bool lists,
+                    Queue&& queue_more, const ReadWords& more, uint2& Ks, int debug, hipStream_t stream) {
+    const int P = p.P;
+    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess_fwd(p, gs, radii, stream), "preprocess");
+    if (prefiltered) GSR_TRY(launch_near_violation(P, p.means3D, p.view, gs.near_flag, stream), "prefiltered check");
+    uint32_t near_flag = 0;
+    Ks = make_uint2(0u, 0u);
+    if (lists) {
+        // K (and what the caller adds) depends on preprocess only: one readback
+        Readback rb;
+        GSR_TRY(rb.begin(stream), "pinned readback buffer");
+        GSR_STAGE(GSR_STAGE_SCAN, launch_count_k_hist(gs, P, true, stream), "count K");
+        if (int rc = queue_more()) return rc;
+        GSR_TRY(rb.copy(0, gs.offsets_K, sizeof(uint32_t)), "memcpy K");
+        if (more.words) GSR_TRY(rb.copy(4, more.src, more.words * sizeof(uint32_t)), "memcpy totals");
+        if (prefiltered) GSR_TRY(rb.copy(1, gs.near_flag, sizeof(uint32_t)), "memcpy prefiltered flag");
+        GSR_TRY(rb.commit(), "event record");
+        // the GPU sorts by depth while the host waits
+        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_depth_sort(gs, P, true, stream), "depth order");
+        GSR_TRY(rb.wait(), "event sync");
+        Ks.x = rb[0];
+        if (prefiltered) near_flag = rb[1];
+        for (int k = 0; k < more.words; k++) more.dst[k] = rb[4 + k];
+    } else {
+        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_depth_sort(gs, P, false, stream), "depth order");
+        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_live_counts(p, gs, radii, stream), "live counts");
+        GSR_STAGE(GSR_STAGE_SCAN, launch_scan(gs, P, stream), "scan");
+        if (int rc = queue_more()) return rc;
+        GSR_TRY(hipMemcpyAsync(&Ks, gs.offsets + (P - 1), sizeof(uint2), hipMemcpyDeviceToHost, stream), "memcpy K");
+        if (more.words)
+            GSR_TRY(hipMemcpyAsync(more.dst, more.src, more.words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+                    "memcpy totals");
+        if (prefiltered)
+            GSR_TRY(hipMemcpyAsync(&near_flag, gs.near_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+                    "memcpy prefiltered flag");
+        hipError_t e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return fail(GSR_ERR_HIP, "stream sync", e);
+    }
+    if (near_flag) return fail(GSR_ERR_ARGS, kPrefilteredMsg);
+    return GSR_OK;
+}
+
+// The per-tile lists (point list and ts.ranges) into the carved binning buffer.
+int build_tile_lists(const FwdParams& p, const GeomState& gs, const int* radii, const BinningState& bs,
+                     const TileState& ts, uint2 Ks, bool lists, int debug, hipStream_t stream) {
+    if (lists) {
+        GSR_STAGE(GSR_STAGE_TILE_LISTS, launch_list_binning(p, gs, radii, bs, ts, (int)Ks.x, stream), "tile lists");
+        return GSR_OK;
+    }
+    const int tiles = (int)(p.grid_x * p.grid_y), K_live = (int)Ks.y;
+    const int tile_bits = (int)higher_msb((uint32_t)tiles);
+    GSR_STAGE(GSR_STAGE_EMIT_KEYS, launch_emit_keys(p, gs, radii, bs, stream), "emit keys");
+    GSR_STAGE(GSR_STAGE_SORT, launch_sort(bs, K_live, tile_bits, stream), "sort");
+    GSR_STAGE(GSR_STAGE_TILE_RANGES, launch_tile_ranges(bs, K_live, ts, tiles, stream), "tile ranges");
+    return GSR_OK;
+}
+
+// A debug getter's tail: the device-to-host copies queued (one with no destination or no bytes is
+// skipped), the stream drained, the error reported as `what`.
+struct HostCopy {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+int copy_to_host(std::initializer_list<HostCopy> copies, hipStream_t stream, const char* what) {
+    hipError_t e = hipSuccess;
+    for (const HostCopy& c : copies)
+        if (e == hipSuccess && c.dst && c.bytes)
+            e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, what, e);
+}
+
 }  // namespace
 
 namespace gsr {
@@ -324,14 +430,9 @@ int gsr_debug_binning(const void* binning_buffer, const void* tile_buffer, int R
     }
     TileState ts{};
     carve_tiles(aligned_base(const_cast<void*>(tile_buffer)), tiles, ts);
-    hipStream_t stream = (hipStream_t)stream_ptr;
-    hipError_t e = hipSuccess;
-    if (point_list_out && R > 0)
-        e = hipMemcpyAsync(point_list_out, bs.point_list, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && ranges_out)
-        e = hipMemcpyAsync(ranges_out, ts.ranges, sizeof(uint2) * tiles, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug binning", e);
+    return copy_to_host({{point_list_out, bs.point_list, sizeof(uint32_t) * R},
+                         {ranges_out, ts.ranges, sizeof(uint2) * tiles}},
+                        (hipStream_t)stream_ptr, "debug binning");
 }
 
 int gsr_debug_sample_points(const void* point_buffer, int PN, float* median_depth_out, uint32_t* last_out,
@@ -339,25 +440,16 @@ int gsr_debug_sample_points(const void* point_buffer, int PN, float* median_dept
     if (!point_buffer || PN < 0) return fail(GSR_ERR_ARGS, "invalid arguments");
     PointState ps;
     carve_points(aligned_base(const_cast<void*>(point_buffer)), PN, ps);
-    hipStream_t stream = (hipStream_t)stream_ptr;
-    hipError_t e = hipSuccess;
-    if (median_depth_out && PN)
-        e = hipMemcpyAsync(median_depth_out, ps.mdepth, sizeof(float) * PN, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && last_out && PN)
-        e = hipMemcpyAsync(last_out, ps.last, sizeof(uint32_t) * PN, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug sample points", e);
+    return copy_to_host({{median_depth_out, ps.mdepth, sizeof(float) * PN}, {last_out, ps.last, sizeof(uint32_t) * PN}},
+                        (hipStream_t)stream_ptr, "debug sample points");
 }
 
 int gsr_debug_image(const void* image_buffer, int width, int height, uint32_t* n_contrib_out, void* stream_ptr) {
     if (!image_buffer || width <= 0 || height <= 0 || !n_contrib_out) return fail(GSR_ERR_ARGS, "invalid arguments");
     ImageState is;
     carve_image(aligned_base(const_cast<void*>(image_buffer)), width * height, is);
-    hipStream_t stream = (hipStream_t)stream_ptr;
-    hipError_t e = hipMemcpyAsync(n_contrib_out, is.n_contrib, sizeof(uint32_t) * (size_t)width * height,
-                                  hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug image", e);
+    return copy_to_host({{n_contrib_out, is.n_contrib, sizeof(uint32_t) * (size_t)width * height}},
+                        (hipStream_t)stream_ptr, "debug image");
 }
 
 int gsr_debug_tile_stats(const void* tile_buffer, int width, int height, uint32_t* max_contrib_out, void* stream_ptr) {
@@ -365,11 +457,8 @@ int gsr_debug_tile_stats(const void* tile_buffer, int width, int height, uint32_
     const int tiles = (int)(((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile));
     TileState ts{};
     carve_tiles(aligned_base(const_cast<void*>(tile_buffer)), tiles, ts);
-    hipStream_t stream = (hipStream_t)stream_ptr;
-    hipError_t e = hipMemcpyAsync(max_contrib_out, ts.max_contrib, sizeof(uint32_t) * (size_t)tiles,
-                                  hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e == hipSuccess ? GSR_OK : fail(GSR_ERR_HIP, "debug tile stats", e);
+    return copy_to_host({{max_contrib_out, ts.max_contrib, sizeof(uint32_t) * (size_t)tiles}},
+                        (hipStream_t)stream_ptr, "debug tile stats");
 }
 
 int gsr_debug_depth_sort_tile_keys(int P) { return P < 0 ? -1 : gsr::dsort_tile_keys(P); }
@@ -506,9 +595,6 @@ const char* gsr_stage_name(int stage) {
 
 const char* gsr_last_error(void) { return g_last_error.c_str(); }
 
-// CR/auxiliary.h:146-148 (the reference traps the kernel)
-static const char* kPrefilteredMsg = "Point is filtered although prefiltered is set. This shouldn't happen!";
-
 int gsr_rasterize_forward_ex2(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
                              gsr_alloc_fn image_alloc, void* image_ctx, gsr_alloc_fn tile_alloc, void* tile_ctx,
                              int P, int sh_degree, int SHM, int sg_degree, int SGM, const float* background, int width,
@@ -537,15 +623,9 @@ int gsr_rasterize_forward_ex2(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc
     // per-Gaussian sort/scan temporaries now, the list-building scratch once
     // K is known), else inside the geometry / binning buffers
     GeomState gs;
-    Carver gtmp(nullptr);
-    void* gbuf = geom_alloc(geom_ctx, carve_geom(nullptr, P, p.grid_x, p.grid_y, gs, scratch_alloc ? &gtmp : nullptr));
-    if (!gbuf) return fail(GSR_ERR_ALLOC, "geometry buffer allocation failed");
-    if (scratch_alloc) {
-        void* sbuf = scratch_alloc(scratch_ctx, gtmp.off + 256);
-        if (!sbuf) return fail(GSR_ERR_ALLOC, "scratch allocation failed");
-        gtmp = Carver(aligned_base(sbuf));
-    }
-    carve_geom(aligned_base(gbuf), P, p.grid_x, p.grid_y, gs, scratch_alloc ? &gtmp : nullptr);
+    if (int rc = carve_alloc_scratch(geom_alloc, geom_ctx, "geometry buffer allocation failed", scratch_alloc,
+                                     scratch_ctx, carve_geom, P, p.grid_x, p.grid_y, gs))
+        return rc;
     TileState ts{};
     if (int rc = carve_alloc(tile_alloc, tile_ctx, "tile buffer allocation failed", carve_tiles, tiles, ts)) return rc;
     ImageState is;
@@ -560,65 +640,22 @@ int gsr_rasterize_forward_ex2(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc
         if (e != hipSuccess) return fail(GSR_ERR_HIP, "memset", e);
         BinningState bs;
         if (int rc = carve_alloc(binning_alloc, binning_ctx, "binning buffer allocation failed", carve_binning, 0, 0,
-                                 p.grid_x, p.grid_y, kBinLists, bs, nullptr))
+                                 p.grid_x, p.grid_y, true, bs, nullptr))
             return rc;
         GSR_TRY(launch_render_fwd(p, gs, bs, is, ts, out_color, out_alpha, out_normal, out_mdepth, stream), "render");
         return GSR_OK;
     }
 
-    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess_fwd(p, gs, radii, stream), "preprocess");
-    if (prefiltered) GSR_TRY(launch_near_violation(P, means3D, viewmatrix, gs.near_flag, stream), "prefiltered check");
-    uint32_t near_flag = 0;
-    const int path = bin_path(p.grid_x, p.grid_y);
-    // K = the reference's instance count (rect tiles): returned as
-    // num_rendered and the capacity of the binning buffer.  The instance-sort
-    // path also needs K_live, the instances that survive tile culling.
-    uint2 Ks = make_uint2(0u, 0u);
-    if (path != kBinInstanceSort) {
-        // K depends on preprocess only: one readback
-        Readback rb;
-        GSR_TRY(rb.begin(stream), "pinned readback buffer");
-        GSR_STAGE(GSR_STAGE_SCAN, launch_count_k_hist(gs, P, path == kBinLists, stream), "count K");
-        GSR_TRY(rb.copy(0, gs.offsets_K, sizeof(uint32_t)), "memcpy K");
-        if (prefiltered) GSR_TRY(rb.copy(1, gs.near_flag, sizeof(uint32_t)), "memcpy prefiltered flag");
-        GSR_TRY(rb.commit(), "event record");
-        // the GPU counts the tile lists (or sorts by depth) while the host waits
-        if (path == kBinLists) GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_depth_sort(gs, P, true, stream), "depth order");
-        GSR_TRY(rb.wait(), "event sync");
-        Ks.x = rb[0];
-        if (prefiltered) near_flag = rb[1];
-    } else {
-        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_depth_sort(gs, P, false, stream), "depth order");
-        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_live_counts(p, gs, radii, stream), "live counts");
-        GSR_STAGE(GSR_STAGE_SCAN, launch_scan(gs, P, stream), "scan");
-        GSR_TRY(hipMemcpyAsync(&Ks, gs.offsets + (P - 1), sizeof(uint2), hipMemcpyDeviceToHost, stream), "memcpy K");
-        if (prefiltered)
-            GSR_TRY(hipMemcpyAsync(&near_flag, gs.near_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
-                    "memcpy prefiltered flag");
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return fail(GSR_ERR_HIP, "stream sync", e);
-    }
-    if (near_flag) return fail(GSR_ERR_ARGS, kPrefilteredMsg);
-    const uint32_t K = Ks.x, K_live = Ks.y;
+    const bool lists = list_binning(p.grid_x, p.grid_y);
+    uint2 Ks;
+    if (int rc = count_instances(p, gs, radii, prefiltered, lists, [] { return GSR_OK; }, ReadWords{}, Ks, debug,
+                                 stream))
+        return rc;
     BinningState bs;
-    Carver btmp(nullptr);
-    void* bbuf = binning_alloc(binning_ctx, carve_binning(nullptr, (int)K, P, p.grid_x, p.grid_y, path, bs,
-                                                          scratch_alloc ? &btmp : nullptr));
-    if (!bbuf) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
-    if (scratch_alloc) {
-        void* sbuf = scratch_alloc(scratch_ctx, btmp.off + 256);
-        if (!sbuf) return fail(GSR_ERR_ALLOC, "scratch allocation failed");
-        btmp = Carver(aligned_base(sbuf));
-    }
-    carve_binning(aligned_base(bbuf), (int)K, P, p.grid_x, p.grid_y, path, bs, scratch_alloc ? &btmp : nullptr);
-    if (path == kBinLists) {
-        GSR_STAGE(GSR_STAGE_TILE_LISTS, launch_list_binning(p, gs, radii, bs, ts, (int)K, stream), "tile lists");
-    } else {
-        const int tile_bits = (int)higher_msb((uint32_t)tiles);
-        GSR_STAGE(GSR_STAGE_EMIT_KEYS, launch_emit_keys(p, gs, radii, bs, stream), "emit keys");
-        GSR_STAGE(GSR_STAGE_SORT, launch_sort(bs, (int)K_live, tile_bits, stream), "sort");
-        GSR_STAGE(GSR_STAGE_TILE_RANGES, launch_tile_ranges(bs, (int)K_live, ts, tiles, stream), "tile ranges");
-    }
+    if (int rc = carve_alloc_scratch(binning_alloc, binning_ctx, "binning buffer allocation failed", scratch_alloc,
+                                     scratch_ctx, carve_binning, (int)Ks.x, P, p.grid_x, p.grid_y, lists, bs))
+        return rc;
+    if (int rc = build_tile_lists(p, gs, radii, bs, ts, Ks, lists, debug, stream)) return rc;
     // Heaviest tile first (LPT, cost = list length) when the grid fills the
     // chip only a few times over: then the last round of long tiles sets the
     // launch's length.  At C3 (8160 tiles, ~5 rounds of 6 blocks per CU) the
@@ -637,7 +674,7 @@ int gsr_rasterize_forward_ex2(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc
         }
         return launch_render_fwd(p, gs, bs, is, ts, out_color, out_alpha, out_normal, out_mdepth, stream);
     }(), "render");
-    if (num_rendered) *num_rendered = (int)K;
+    if (num_rendered) *num_rendered = (int)Ks.x;
     return GSR_OK;
 }
 
@@ -671,13 +708,13 @@ int gsr_rasterize_forward(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn 
                           const float* cam_pos, float tan_fovx, float tan_fovy, float kernel_size, int prefiltered,
                           float* out_color, float* out_mdepth, float* out_alpha, float* out_normal, int* radii,
                           int require_depth, int debug, void* stream_ptr, int* num_rendered) {
-    return gsr_rasterize_forward_ex(geom_alloc, geom_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx,
-                                    tile_alloc, tile_ctx, P, sh_degree, SHM, sg_degree, SGM, background, width,
-                                    height, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                    shs, sg_axis, sg_sharpness, sg_color, scale_modifier, viewmatrix, projmatrix,
-                                    cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color, out_mdepth,
-                                    out_alpha, out_normal, radii, require_depth, debug, stream_ptr, num_rendered,
-                                    nullptr, nullptr);
+    return gsr_rasterize_forward_ex2(geom_alloc, geom_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx,
+                                     tile_alloc, tile_ctx, P, sh_degree, SHM, sg_degree, SGM, background, width,
+                                     height, means3D, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                     shs, sg_axis, sg_sharpness, sg_color, scale_modifier, viewmatrix, projmatrix,
+                                     cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color, out_mdepth,
+                                     out_alpha, out_normal, radii, require_depth, debug, stream_ptr, num_rendered,
+                                     nullptr, nullptr, nullptr);
 }
 
 int gsr_rasterize_backward_ex2(gsr_alloc_fn geom_bwd_alloc, void* geom_bwd_ctx, int P, int sh_degree, int SHM,
@@ -746,17 +783,15 @@ int gsr_rasterize_backward_ex2(gsr_alloc_fn geom_bwd_alloc, void* geom_bwd_ctx, 
     carve_geom(aligned_base(const_cast<void*>(geom_buffer)), P, b.f.grid_x, b.f.grid_y, gs);
     BinningState bs;  // (the backward reads the point list only: first in every layout)
     carve_binning(aligned_base(const_cast<void*>(binning_buffer)), R, P, b.f.grid_x, b.f.grid_y,
-                  bin_path(b.f.grid_x, b.f.grid_y), bs);
+                  list_binning(b.f.grid_x, b.f.grid_y), bs);
     ImageState is;
     carve_image(aligned_base(const_cast<void*>(image_buffer)), width * height, is);
     TileState ts{};
     carve_tiles(aligned_base(const_cast<void*>(tile_buffer)), tiles, ts);
     BwdState ws{};
-    const size_t wbytes = carve_bwd(nullptr, P, ws, tiles);
-    void* wbuf = geom_bwd_alloc(geom_bwd_ctx, wbytes + 256);
-    if (!wbuf) return fail(GSR_ERR_ALLOC, "backward buffer allocation failed");
-    void* wb = aligned_base(wbuf);
-    carve_bwd(wb, P, ws, tiles);
+    void* wb = nullptr;
+    size_t wbytes = 0;
+    if (int rc = alloc_bwd(geom_bwd_alloc, geom_bwd_ctx, P, tiles, ws, wb, wbytes)) return rc;
     if (tiles > 0) {
         // heaviest tiles first (cost: the forward's per-tile max contributor),
         // ordered by one workgroup while the others clear the accumulators
@@ -818,15 +853,15 @@ int gsr_rasterize_backward(gsr_alloc_fn geom_bwd_alloc, void* geom_bwd_ctx, int 
                            float* dL_dscale, float* dL_drot, float* dL_dcov3D, float* dL_dsh, float* dL_dsg_axis,
                            float* dL_dsg_sharpness, float* dL_dsg_color, int require_depth, int debug,
                            void* stream_ptr) {
-    return gsr_rasterize_backward_ex(geom_bwd_alloc, geom_bwd_ctx, P, sh_degree, SHM, sg_degree, SGM, R, background,
-                                     width, height, means3D, colors_precomp, opacities, scales, rotations,
-                                     cov3D_precomp, shs, sg_axis, sg_sharpness, sg_color, scale_modifier, viewmatrix,
-                                     projmatrix, campos, tan_fovx, tan_fovy, kernel_size, radii, alphas, normalmap,
-                                     mdepth, geom_buffer, binning_buffer, image_buffer, tile_buffer, dL_dpix,
-                                     dL_dpix_mdepth, dL_dalphas, dL_dpixel_normals, dL_dmean3D, dL_dmean2D, dL_dcolor,
-                                     dL_dopacity, dL_dscale, dL_drot, dL_dcov3D, dL_dsh, dL_dsg_axis,
-                                     dL_dsg_sharpness, dL_dsg_color, require_depth, debug, 1, nullptr, nullptr,
-                                     nullptr, stream_ptr);
+    return gsr_rasterize_backward_ex2(geom_bwd_alloc, geom_bwd_ctx, P, sh_degree, SHM, sg_degree, SGM, R, background,
+                                      width, height, means3D, colors_precomp, opacities, scales, rotations,
+                                      cov3D_precomp, shs, sg_axis, sg_sharpness, sg_color, scale_modifier, viewmatrix,
+                                      projmatrix, campos, tan_fovx, tan_fovy, kernel_size, radii, alphas, normalmap,
+                                      mdepth, geom_buffer, binning_buffer, image_buffer, tile_buffer, dL_dpix,
+                                      dL_dpix_mdepth, dL_dalphas, dL_dpixel_normals, dL_dmean3D, dL_dmean2D,
+                                      dL_dcolor, dL_dopacity, dL_dscale, dL_drot, dL_dcov3D, dL_dsh, dL_dsg_axis,
+                                      dL_dsg_sharpness, dL_dsg_color, require_depth, debug, 1, nullptr, nullptr,
+                                      nullptr, stream_ptr, nullptr, nullptr);
 }
 
 // The point-query forwards (sample_depth, integrate, evaluate_sdf) share
@@ -866,17 +901,11 @@ static int point_query_forward(int query, gsr_alloc_fn geom_alloc, void* geom_ct
         return fail(GSR_ERR_ARGS, "missing allocator");
     const uint32_t tiles = p.grid_x * p.grid_y;
 
-    // forward-only scratch as in gsr_rasterize_forward_ex
+    // forward-only scratch as in gsr_rasterize_forward_ex2
     GeomState gs;
-    Carver gtmp(nullptr);
-    void* gbuf = geom_alloc(geom_ctx, carve_geom(nullptr, P, p.grid_x, p.grid_y, gs, scratch_alloc ? &gtmp : nullptr));
-    if (!gbuf) return fail(GSR_ERR_ALLOC, "geometry buffer allocation failed");
-    if (scratch_alloc) {
-        void* sbuf = scratch_alloc(scratch_ctx, gtmp.off + 256);
-        if (!sbuf) return fail(GSR_ERR_ALLOC, "scratch allocation failed");
-        gtmp = Carver(aligned_base(sbuf));
-    }
-    carve_geom(aligned_base(gbuf), P, p.grid_x, p.grid_y, gs, scratch_alloc ? &gtmp : nullptr);
+    if (int rc = carve_alloc_scratch(geom_alloc, geom_ctx, "geometry buffer allocation failed", scratch_alloc,
+                                     scratch_ctx, carve_geom, P, p.grid_x, p.grid_y, gs))
+        return rc;
     TileState ts{};
     SampleTiles st;
     if (int rc = carve_alloc(tile_alloc, tile_ctx, "tile buffer allocation failed", carve_sample_tiles, (int)tiles, ts, st))
@@ -888,75 +917,35 @@ static int point_query_forward(int query, gsr_alloc_fn geom_alloc, void* geom_ct
                              carve_point_binning, PN, tiles, pb))
         return rc;
 
-    GSR_STAGE(GSR_STAGE_PREPROCESS, launch_preprocess_fwd(p, gs, gs.radii, stream), "preprocess");
-    if (prefiltered) GSR_TRY(launch_near_violation(P, means3D, viewmatrix, gs.near_flag, stream), "prefiltered check");
-    uint32_t near_flag = 0;
-    const int path = bin_path(p.grid_x, p.grid_y);  // as the render forward
-    uint2 Ks = make_uint2(0u, 0u);
+    // the Gaussian side as the render forward; the point totals (points kept, duplicated tiles, chunks)
+    // depend on the points only and are read back with K
+    const bool lists = list_binning(p.grid_x, p.grid_y);
+    uint2 Ks;
     uint32_t totals[4] = {0, 0, 0, 0};
-    if (path != kBinInstanceSort) {
-        // K, the tile list sizes and the point totals depend on preprocess and
-        // the points only: one readback
-        Readback rb;
-        GSR_TRY(rb.begin(stream), "pinned readback buffer");
-        GSR_STAGE(GSR_STAGE_SCAN, launch_count_k_hist(gs, P, path == kBinLists, stream), "count K");
+    auto queue_points = [&]() -> int {
         GSR_STAGE(GSR_STAGE_SAMPLE_POINTS, launch_sample_points(p, PN, points3D, ps, pb, st, stream), "sample points");
         GSR_STAGE(GSR_STAGE_SAMPLE_POINTS, launch_sample_setup(PN, tiles, pb, st, stream), "sample setup");
-        GSR_TRY(rb.copy(0, gs.offsets_K, sizeof(uint32_t)), "memcpy K");
-        GSR_TRY(rb.copy(4, st.totals, 4 * sizeof(uint32_t)), "memcpy totals");
-        if (prefiltered) GSR_TRY(rb.copy(1, gs.near_flag, sizeof(uint32_t)), "memcpy prefiltered flag");
-        GSR_TRY(rb.commit(), "event record");
-        // the GPU counts the tile lists (or sorts by depth) while the host waits
-        if (path == kBinLists) GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_depth_sort(gs, P, true, stream), "depth order");
-        GSR_TRY(rb.wait(), "event sync");
-        Ks.x = rb[0];
-        if (prefiltered) near_flag = rb[1];
-        for (int k = 0; k < 4; k++) totals[k] = rb[4 + k];
-    } else {
-        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_depth_sort(gs, P, false, stream), "depth order");
-        GSR_STAGE(GSR_STAGE_DEPTH_ORDER, launch_live_counts(p, gs, gs.radii, stream), "live counts");
-        GSR_STAGE(GSR_STAGE_SCAN, launch_scan(gs, P, stream), "scan");
-        GSR_STAGE(GSR_STAGE_SAMPLE_POINTS, launch_sample_points(p, PN, points3D, ps, pb, st, stream), "sample points");
-        GSR_STAGE(GSR_STAGE_SAMPLE_POINTS, launch_sample_setup(PN, tiles, pb, st, stream), "sample setup");
-        GSR_TRY(hipMemcpyAsync(&Ks, gs.offsets + (P - 1), sizeof(uint2), hipMemcpyDeviceToHost, stream), "memcpy K");
-        GSR_TRY(hipMemcpyAsync(totals, st.totals, sizeof(totals), hipMemcpyDeviceToHost, stream), "memcpy totals");
-        if (prefiltered)
-            GSR_TRY(hipMemcpyAsync(&near_flag, gs.near_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
-                    "memcpy prefiltered flag");
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return fail(GSR_ERR_HIP, "stream sync", e);
-    }
-    if (near_flag) return fail(GSR_ERR_ARGS, kPrefilteredMsg);
-    const uint32_t K = Ks.x, K_live = Ks.y, n_chunks = totals[2];
+        return GSR_OK;
+    };
+    if (int rc = count_instances(p, gs, gs.radii, prefiltered, lists, queue_points, ReadWords{st.totals, 4, totals}, Ks,
+                                 debug, stream))
+        return rc;
+    const uint32_t n_chunks = totals[2];
     BinningState bs;
-    Carver btmp(nullptr);
-    void* bbuf = binning_alloc(binning_ctx, carve_binning(nullptr, (int)K, P, p.grid_x, p.grid_y, path, bs,
-                                                          scratch_alloc ? &btmp : nullptr));
-    if (!bbuf) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
-    if (scratch_alloc) {
-        void* sbuf = scratch_alloc(scratch_ctx, btmp.off + 256);
-        if (!sbuf) return fail(GSR_ERR_ALLOC, "scratch allocation failed");
-        btmp = Carver(aligned_base(sbuf));
-    }
-    carve_binning(aligned_base(bbuf), (int)K, P, p.grid_x, p.grid_y, path, bs, scratch_alloc ? &btmp : nullptr);
+    if (int rc = carve_alloc_scratch(binning_alloc, binning_ctx, "binning buffer allocation failed", scratch_alloc,
+                                     scratch_ctx, carve_binning, (int)Ks.x, P, p.grid_x, p.grid_y, lists, bs))
+        return rc;
     ChunkState cs{};
     if (int rc = carve_alloc(dup_tile_alloc, dup_tile_ctx, "duplicated-tile buffer allocation failed", carve_chunks,
                              n_chunks, cs))
         return rc;
-    if (path == kBinLists) {
-        GSR_STAGE(GSR_STAGE_TILE_LISTS, launch_list_binning(p, gs, gs.radii, bs, ts, (int)K, stream), "tile lists");
-    } else {
-        const int tile_bits = (int)higher_msb(tiles);
-        GSR_STAGE(GSR_STAGE_EMIT_KEYS, launch_emit_keys(p, gs, gs.radii, bs, stream), "emit keys");
-        GSR_STAGE(GSR_STAGE_SORT, launch_sort(bs, (int)K_live, tile_bits, stream), "sort");
-        GSR_STAGE(GSR_STAGE_TILE_RANGES, launch_tile_ranges(bs, (int)K_live, ts, (int)tiles, stream), "tile ranges");
-    }
+    if (int rc = build_tile_lists(p, gs, gs.radii, bs, ts, Ks, lists, debug, stream)) return rc;
     // (heaviest-first chunk order with the tile's list length as the cost
     // was measured for this forward: no change, 1.52 vs 1.51 ms at 1.27M points)
     GSR_STAGE(GSR_STAGE_SAMPLE_FWD,
               launch_point_fwd(query, p, gs, bs, ts, ps, pb, st, cs, n_chunks, output, output2, inside, stream),
               "point query");
-    if (num_rendered) *num_rendered = (int)K;
+    if (num_rendered) *num_rendered = (int)Ks.x;
     if (num_points) *num_points = (int)totals[0];
     if (num_duplicated_tiles) *num_duplicated_tiles = (int)totals[1];
     return GSR_OK;
@@ -1075,7 +1064,7 @@ int gsr_sample_depth_backward(gsr_alloc_fn geom_bwd_alloc, void* geom_bwd_ctx, i
     carve_geom(aligned_base(const_cast<void*>(geom_buffer)), P, b.f.grid_x, b.f.grid_y, gs);
     BinningState bs;  // (the backward reads the point list only: first in every layout)
     carve_binning(aligned_base(const_cast<void*>(binning_buffer)), R, P, b.f.grid_x, b.f.grid_y,
-                  bin_path(b.f.grid_x, b.f.grid_y), bs);
+                  list_binning(b.f.grid_x, b.f.grid_y), bs);
     PointState ps;
     carve_points(aligned_base(const_cast<void*>(point_buffer)), PN, ps);
     PointBinState pb;
@@ -1090,11 +1079,9 @@ int gsr_sample_depth_backward(gsr_alloc_fn geom_bwd_alloc, void* geom_bwd_ctx, i
     }
     BwdState ws{};
     const uint32_t bound = PN > 0 ? sample_chunk_bound(PN, tiles) : 0u;
-    const size_t wbytes = carve_bwd(nullptr, P, ws, (int)bound);
-    void* wbuf = geom_bwd_alloc(geom_bwd_ctx, wbytes + 256);
-    if (!wbuf) return fail(GSR_ERR_ALLOC, "backward buffer allocation failed");
-    void* wb = aligned_base(wbuf);
-    carve_bwd(wb, P, ws, (int)bound);
+    void* wb = nullptr;
+    size_t wbytes = 0;
+    if (int rc = alloc_bwd(geom_bwd_alloc, geom_bwd_ctx, P, (int)bound, ws, wb, wbytes)) return rc;
     GSR_STAGE(GSR_STAGE_BWD_CLEAR, hipMemsetAsync(wb, 0, wbytes, stream), "memset accumulators");
     if (bound)  // heaviest chunks first (cost: the forward's chunk max contributor)
         GSR_STAGE(GSR_STAGE_BWD_CLEAR, launch_chunk_order(bound, st.totals + 2, cs.chunk_max, ws.tile_order, stream),

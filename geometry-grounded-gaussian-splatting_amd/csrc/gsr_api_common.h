@@ -200,5 +200,24 @@ int carve_alloc(gsr_alloc_fn alloc, void* ctx, const char* what, size_t (*carve)
     return GSR_OK;
 }
 
+// carve_alloc for a carve whose last parameter, after `args`, is `Carver* tmp`: where its forward-only
+// fields go.  With `scratch` they come out of a block of their own, requested after the buffer itself and
+// carved from its aligned base; with `scratch` NULL tmp is NULL and they sit at the end of the buffer.
+template <class Carve, class... A>
+int carve_alloc_scratch(gsr_alloc_fn alloc, void* ctx, const char* what, gsr_alloc_fn scratch, void* scratch_ctx,
+                        Carve carve, A&&... args) {
+    Carver tmp(nullptr);
+    Carver* t = scratch ? &tmp : nullptr;
+    void* buf = alloc(ctx, carve(nullptr, args..., t));
+    if (!buf) return fail(GSR_ERR_ALLOC, what);
+    if (scratch) {
+        void* sbuf = scratch(scratch_ctx, tmp.off + 256);
+        if (!sbuf) return fail(GSR_ERR_ALLOC, "scratch allocation failed");
+        tmp = Carver(aligned_base(sbuf));
+    }
+    carve(aligned_base(buf), args..., t);
+    return GSR_OK;
+}
+
 }  // namespace
 }  // namespace gsr

@@ -86,15 +86,12 @@ struct GeomState {
 inline int tile_key_bytes(int tile_bits) { return tile_bits <= 16 ? 2 : 4; }
 // Tile-list binning (tilelists.hip): grids up to kMaxGrid x kMaxGrid tiles.
 constexpr int kMaxGrid = 1024;
-enum BinPath : int { kBinInstanceSort = 0, kBinLists = 1 };
 struct ListLayout {
     int nseg_rows = 0, nseg_tiles_max = 0, rowseg = 64;
     size_t tmp_bytes = 0;
 };
 struct BinningState {
     uint32_t* point_list;  // first in the buffer: its offset depends on nothing else
-    int path;              // BinPath
-    bool use_lists;        // tilelists.hip path
     ListLayout lists;
     uint2* rows;           // (Gaussian, column span) per tile row, q order
     uint4* qrec;           // [P][2] per Gaussian in q order: id, rows y0 | y1 << 16, spans of rows y0 .. y0 + 5

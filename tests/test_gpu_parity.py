@@ -661,6 +661,150 @@ def test_forward_scratch_split_is_exact(monkeypatch):
     assert split[0][7].numel() < whole[0][7].numel()  # binning buffer
 
 
+_OLDER = {}
+
+
+def _older_case():
+    """The scene of test_forward_scratch_split_is_exact with what the older entry points are held to, computed
+    once: the `_C` path (gsr_rasterize_{forward,backward}_ex2) with the binding's scratch allocator (`split`)
+    and with a NULL one (`whole`, gsr_rasterize_forward's layout), and `whole`'s gradients."""
+    from diff_gaussian_rasterization import _C
+
+    if _OLDER:
+        return _OLDER
+    c = Hh.small_case(P=4000, W=200, H=120, seed=5, log_scale=math.log(0.03))
+    ga = [_gpu(x) for x in _fwd_args(c)] + [False]
+    g = {k: _gpu(v) for k, v in S.upstream_grads(120, 200).items()}
+
+    class _NoScratch:  # a NULL scratch allocator
+        def __init__(self, _dev):
+            self.cb = _C._ALLOC()
+
+    split = _C.rasterize_gaussians(*ga)
+    saved, _C._ScratchBlocks = _C._ScratchBlocks, _NoScratch
+    try:
+        whole = _C.rasterize_gaussians(*ga)
+    finally:
+        _C._ScratchBlocks = saved
+    K, color, alpha, normal, mdepth, radii = whole[:6]
+    grads = _C.rasterize_gaussians_backward(*ga[:19], g["color"], g["mdepth"], None, g["normal"], alpha, normal, mdepth,
+                                            ga[21], radii, whole[6], K, whole[7], whole[8], whole[9], True, False)
+    _OLDER.update(ga=ga, g=g, split=split, whole=whole, grads=grads, lists=_live_lists(whole))
+    return _OLDER
+
+
+def _live_lists(out):
+    """(live point list, ranges) of a forward's buffers (past the live entries the capacity is unwritten)."""
+    from diff_gaussian_rasterization import _C
+
+    plist, ranges = _C.debug_binning(out[7], out[9], out[0], 120, 200)
+    return plist[:int(ranges[:, 1].max())].copy(), ranges
+
+
+def _scene_pointers(ga):
+    """The C ABI's scene arguments from P to kernel_size (shared by the forward and the backward), with the
+    tensors that hold them alive."""
+    from diff_gaussian_rasterization import _C
+
+    (bg, means3D, colors, opac, scales, rots, cov, sh, sga, sgs, sgc, shd, sgd, smod, view, proj, tanx, tany, ks, H, W,
+     campos) = ga[:22]
+    keep = [t.contiguous()
+            for t in (bg, means3D, colors, opac, scales, rots, cov, sh, sga, sgs, sgc, view, proj, campos)]
+    p = [_C._ptr(t) for t in keep]
+    P, SHM, SGM = means3D.size(0), sh.size(1) if sh.numel() else 0, sgc.size(1) if sgc.numel() else 0
+    head = [P, int(shd), SHM, int(sgd), SGM]
+    tail = [p[0], int(W), int(H), *p[1:11], float(smod), *p[11:14], float(tanx), float(tany), float(ks)]
+    return head, tail, keep
+
+
+def _direct_forward(name, ga, *extra):
+    """gsr_rasterize_forward (or, with `extra` = its scratch allocator and context, gsr_rasterize_forward_ex)
+    called as a C host calls it, `Out` buffers as the allocators: the tuple of _C.rasterize_gaussians."""
+    import ctypes
+
+    from diff_gaussian_rasterization import _C
+
+    head, tail, keep = _scene_pointers(ga)
+    H, W, P = int(ga[19]), int(ga[20]), head[0]
+    fopt = dict(dtype=torch.float32, device=DEV)
+    color, mdepth, alpha, normal = (torch.empty(n, H, W, **fopt) for n in (3, 1, 1, 3))
+    radii = torch.empty(P, dtype=torch.int32, device=DEV)
+    bufs = [_C.Out(DEV, torch.uint8) for _ in range(4)]
+    K = ctypes.c_int(0)
+    _C.call(DEV, name, bufs[0].cb, None, bufs[1].cb, None, bufs[2].cb, None, bufs[3].cb, None, *head, *tail,
+            int(bool(ga[22])), _C._ptr(color), _C._ptr(mdepth), _C._ptr(alpha), _C._ptr(normal), _C._ptr(radii),
+            int(bool(ga[23])), 0, _C._stream(DEV), ctypes.byref(K), *extra)
+    del keep
+    return (K.value, color, alpha, normal, mdepth, radii, *[b.tensor for b in bufs])
+
+
+def _direct_backward(name, ga, g, out, *extra):
+    """gsr_rasterize_backward (or, with `extra` = chunks, on_chunk, chunk_ctx, dc_rows, gsr_rasterize_backward_ex)
+    on the forward `out`: the gradients in _C.rasterize_gaussians_backward's order."""
+    from diff_gaussian_rasterization import _C
+
+    head, tail, keep = _scene_pointers(ga)
+    P, SHM, SGM = head[0], head[2], head[4]
+    K, color, alpha, normal, mdepth, radii, geom, binning, image, tile = out
+    fopt = dict(dtype=torch.float32, device=DEV)
+    d = {k: torch.empty(*shape, **fopt) for k, shape in dict(
+        dmeans3D=(P, 3), dmeans2D=(P, 3), dcolors=(P, 3), dopacity=(P, 1), dscales=(P, 3), drotations=(P, 4),
+        dcov3D=(P, 6), dsh=(P, SHM, 3), dsg_axis=(P, SGM, 3), dsg_sharpness=(P, SGM), dsg_color=(P, SGM, 3)).items()}
+    scratch = _C.Out(DEV, torch.uint8)
+    _C.call(DEV, name, scratch.cb, None, *head, int(K), *tail, _C._ptr(radii), _C._ptr(alpha), _C._ptr(normal),
+            _C._ptr(mdepth), _C._ptr(geom), _C._ptr(binning), _C._ptr(image), _C._ptr(tile), _C._ptr(g["color"]),
+            _C._ptr(g["mdepth"]), None, _C._ptr(g["normal"]),
+            *[_C._ptr(d[k]) for k in ("dmeans3D", "dmeans2D", "dcolors", "dopacity", "dscales", "drotations", "dcov3D",
+                                      "dsh", "dsg_axis", "dsg_sharpness", "dsg_color")],
+            int(bool(ga[23])), 0, *extra, _C._stream(DEV))
+    torch.cuda.synchronize()
+    del keep, scratch
+    return [d[k] for k in GRAD_NAMES]
+
+
+@pytest.mark.parametrize("name", ["gsr_rasterize_forward", "gsr_rasterize_forward_ex"])
+def test_older_forward_entry_points(name):
+    """The documented C entry points that the binding does not call, called directly through the loaded
+    library: gsr_rasterize_forward, and gsr_rasterize_forward_ex with a scratch allocator, give the K, the
+    images, the live point list and the tile ranges of the `_C` path (gsr_rasterize_forward_ex2) under a NULL
+    scratch allocator, bit for bit.  The four saved buffers have the sizes of the `_C` path with the same
+    kind of scratch allocator: with one, the geometry and binning buffers are smaller by design
+    (test_forward_scratch_split_is_exact), so gsr_rasterize_forward_ex's are held to the `_C` path with the
+    binding's allocator and gsr_rasterize_forward's to the NULL one."""
+    from diff_gaussian_rasterization import _C
+
+    o = _older_case()
+    if name == "gsr_rasterize_forward":
+        out, sizes = _direct_forward(name, o["ga"]), o["whole"]
+    else:
+        scratch = _C._ScratchBlocks(DEV)
+        out, sizes = _direct_forward(name, o["ga"], scratch.cb, None), o["split"]
+        assert len(scratch.blocks) == 2  # the per-Gaussian block and the list-building block
+    assert out[0] == o["whole"][0]
+    for a, b in zip(out[1:6], o["whole"][1:6]):
+        assert torch.equal(a, b)
+    assert [t.numel() for t in out[6:10]] == [t.numel() for t in sizes[6:10]]
+    plist, ranges = _live_lists(out)
+    assert np.array_equal(plist, o["lists"][0]) and np.array_equal(ranges, o["lists"][1])
+
+
+@pytest.mark.parametrize("name", ["gsr_rasterize_backward", "gsr_rasterize_backward_ex"])
+def test_older_backward_entry_points(name):
+    """gsr_rasterize_backward, and gsr_rasterize_backward_ex with chunks = 1 and no callback, on the buffers
+    of a plain gsr_rasterize_forward: the gradients of the `_C` path (gsr_rasterize_backward_ex2) within the
+    bound of test_forward_scratch_split_is_exact for order-dependent float atomics, 1e-5 max|ref| per tensor."""
+    from diff_gaussian_rasterization import _C
+
+    o = _older_case()
+    out = _direct_forward("gsr_rasterize_forward", o["ga"])
+    extra = () if name == "gsr_rasterize_backward" else (1, _C._CHUNK(), None, None)
+    grads = _direct_backward(name, o["ga"], o["g"], out, *extra)
+    for gname, a, b in zip(GRAD_NAMES, grads, o["grads"]):
+        assert a.shape == b.shape, gname
+        if b.numel():
+            assert float((a - b).abs().max()) <= 1e-5 * max(float(b.abs().max()), 1e-30), gname
+
+
 def test_autograd_render_end_to_end():
     """gaussian_renderer.render() -> GaussianRasterizer -> autograd, with the
     GaussianModel getters in front: gradients reach the raw parameters and the

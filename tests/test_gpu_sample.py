@@ -140,6 +140,42 @@ def test_sample_scratch_split_is_exact(monkeypatch):
     assert split[0][6].numel() < whole[0][6].numel()  # binning buffer
 
 
+def test_older_sample_forward_entry_point(monkeypatch):
+    """gsr_sample_depth_forward, the documented entry point the binding does not call, called directly through
+    the loaded library with `Out` buffers as the allocators: the points, flags, three counts and six buffer
+    sizes of _C.sample_rasterized_depth (gsr_sample_depth_forward_ex) under a NULL scratch allocator, bit for
+    bit."""
+    import ctypes
+
+    from diff_gaussian_rasterization import _C
+
+    c = Hh.small_case(P=2000, W=160, H=96, seed=2, log_scale=math.log(0.05))
+    pts = sample_points(c, 20000, 102)
+    ga = [_gpu(x) for x in sample_args(c, pts)] + [False]
+
+    class _NoScratch:  # a NULL scratch allocator: gsr_sample_depth_forward's layout
+        def __init__(self, _dev):
+            self.cb = _C._ALLOC()
+
+    monkeypatch.setattr(_C, "_ScratchBlocks", _NoScratch)
+    ref = _C.sample_rasterized_depth(*ga)
+
+    points3D, means3D, opac, scales, rots, smod, cov, view, proj, tanx, tany, ks, H, W, campos, prefiltered = ga[:16]
+    keep = [t.contiguous() for t in (points3D, means3D, opac, scales, rots, cov, view, proj, campos)]
+    p = [_C._ptr(t) for t in keep]
+    output = torch.zeros_like(points3D)
+    inside = torch.zeros(points3D.shape[:-1], dtype=torch.bool, device=DEV)
+    bufs = [_C.Out(DEV, torch.uint8) for _ in range(6)]
+    K, RN, TN = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _C.call(DEV, "gsr_sample_depth_forward", *[x for b in bufs for x in (b.cb, None)], points3D.numel() // 3,
+            means3D.size(0), int(W), int(H), *p[:4], float(smod), *p[4:], float(tanx), float(tany), float(ks),
+            int(bool(prefiltered)), _C._ptr(output), _C._ptr(inside), 0, _C._stream(DEV), ctypes.byref(K),
+            ctypes.byref(RN), ctypes.byref(TN))
+    assert (K.value, RN.value, TN.value) == ref[:3]
+    assert torch.equal(output, ref[3]) and torch.equal(inside, ref[4])
+    assert [b.tensor.numel() for b in bufs] == [t.numel() for t in ref[5:11]]
+
+
 def test_sample_parity_batched_shape_and_kernel_size():
     """points3D of shape [H, W, 3] (the training call); forward with kernel
     size 0.0 and backward with the settings' 0.1, as the reference wrapper
