@@ -182,24 +182,6 @@ __device__ __forceinline__ void ds_store(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// exclusive scan of one value per lane over the first 256 lanes of the
-// block (every lane calls it: it holds a barrier); s_w: 4 words
-__device__ __forceinline__ uint32_t ds_digit_excl(uint32_t v, uint32_t* s_w) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63 && wave < 4) s_w[wave] = x;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) before += w < wave ? s_w[w] : 0u;
-    return before + x - v;
-}
-
 template <int PASS, int ITEMS>
 __global__ void __launch_bounds__(kDsThreads) dsort_pass_kernel(const uint32_t* __restrict__ keys_in,
                                                                 const uint32_t* __restrict__ vals_in, int P,
@@ -262,7 +244,8 @@ __global__ void __launch_bounds__(kDsThreads) dsort_pass_kernel(const uint32_t* 
         ds_store(st + (size_t)tile * 256, (tile == 0 ? kDsInc : kDsAgg) | cnt);
     }
     // (digit 255's count, with or without the padding, enters no prefix)
-    const uint32_t pre = ds_digit_excl(cnt, s_w);
+    // (over the first 256 lanes of the block: one per digit; every lane calls it)
+    const uint32_t pre = block_excl_scan<4>(cnt, s_w);
     if (dl) s_pre[d] = pre;
     __syncthreads();
     // 3. keys and values to LDS in tile-sorted order (while the preceding tiles publish)
@@ -325,7 +308,7 @@ __global__ void __launch_bounds__(kDsThreads) dsort_pass_kernel(const uint32_t* 
     }
     __syncthreads();
     // global digit start: exclusive scan of the whole-input histogram, plus the preceding tiles
-    const uint32_t gpre = ds_digit_excl(dl ? s.hist[PASS * 256 + d] : 0u, s_w);
+    const uint32_t gpre = block_excl_scan<4>(dl ? s.hist[PASS * 256 + d] : 0u, s_w);
     if (dl) s_goff[d] = gpre + s_excl[d];
     __syncthreads();
     const int nvalid = min(kTile, P - tile * kTile);

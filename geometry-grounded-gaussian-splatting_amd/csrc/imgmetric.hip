@@ -51,17 +51,6 @@ __device__ __forceinline__ unsigned quantize8(float x) {
 // torch.clamp(x, 0, 1): NaN stays NaN
 __device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct ImageMetricsParams {
     int C, H, W;
     const float* render;  // [N, C, H, W]
@@ -209,14 +198,14 @@ __global__ void __launch_bounds__(256) image_metrics_kernel(ImageMetricsParams q
                 const double den1 = mu1_sq + mu2_sq + kImC1, den2 = s1 + s2 + kImC2;
                 sum += (num1 * num2) / (den1 * den2);
             }
-            sum = wave_sum_d(sum);
+            sum = wave_sum(sum);
         }
         if (QUANT) {
-            u1 = wave_sum_u(u1);
-            u2 = wave_sum_u(u2);
+            u1 = wave_sum(u1);
+            u2 = wave_sum(u2);
         } else {
-            d1 = wave_sum_d(d1);
-            d2 = wave_sum_d(d2);
+            d1 = wave_sum(d1);
+            d2 = wave_sum(d2);
         }
         if ((tid & 63) == 0) {
             s_red[tid >> 6] = sum;
@@ -269,14 +258,7 @@ __global__ void __launch_bounds__(1024)
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ss += __shfl_xor(ss, o, 64);
-        a1 += __shfl_xor(a1, o, 64);
-        a2 += __shfl_xor(a2, o, 64);
-        i1 += __shfl_xor(i1, o, 64);
-        i2 += __shfl_xor(i2, o, 64);
-    }
+    ss = wave_sum(ss), a1 = wave_sum(a1), a2 = wave_sum(a2), i1 = wave_sum(i1), i2 = wave_sum(i2);
     if (lane == 0) {
         s_s[wave] = ss;
         s_1[wave] = a1;

@@ -57,30 +57,6 @@ size_t carve_knn(void* base, int P, KnnState& s) {
     return c.off + 256;
 }
 
-// min / max of the six bound values over a 256-lane block (fminf/fmaxf are
-// exact, so the reduction order does not matter)
-__device__ inline void block_minmax6(float (&v)[6], float (*s)[6]) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const float u = __shfl_xor(v[k], o, 64);
-            v[k] = k < 3 ? fminf(v[k], u) : fmaxf(v[k], u);
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) s[wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const float a = s[0][k], b = s[1][k], c = s[2][k], d = s[3][k];
-        v[k] = k < 3 ? fminf(fminf(a, b), fminf(c, d)) : fmaxf(fmaxf(a, b), fmaxf(c, d));
-    }
-}
-
 __global__ void __launch_bounds__(256) knn_bounds_kernel(int P, const float* __restrict__ pts,
                                                          float* __restrict__ partials) {
     __shared__ float s[4][6];

@@ -332,7 +332,7 @@ __device__ __forceinline__ void pm_block_sums(float (&v)[4], float* out) {
     __shared__ float s[4][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = wave_sum_f(v[k]);
+    for (int k = 0; k < 4; k++) v[k] = wave_sum(v[k]);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 4; k++) s[wave][k] = v[k];
@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(1024) pm_finish_kernel(const float* __restrict
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = wave_sum_f(v[k]);
+    for (int k = 0; k < 4; k++) v[k] = wave_sum(v[k]);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 4; k++) s[wave][k] = v[k];

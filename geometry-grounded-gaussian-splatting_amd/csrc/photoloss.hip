@@ -171,8 +171,8 @@ __global__ void __launch_bounds__(256)
         }
     }
     const int nq = 2 + (want_emb ? (q.mode == kAppGS ? 4 : q.mode == kAppPGSR ? 2 : 0) : 0);
-    sum = wave_sum_f(sum);
-    l1 = wave_sum_f(l1);
+    sum = wave_sum(sum);
+    l1 = wave_sum(l1);
     if ((tid & 63) == 0) {
         s_red[0][tid >> 6] = sum;
         s_red[1][tid >> 6] = l1;
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(256)
     if (nq > 2) {
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const float v = wave_sum_f(es[k]);
+            const float v = wave_sum(es[k]);
             if ((tid & 63) == 0) s_red[2 + k][tid >> 6] = v;
         }
     }
@@ -197,8 +197,7 @@ __device__ __forceinline__ double photo_block_sum(const float* __restrict__ p, i
     double acc = 0.0;
     for (int k = threadIdx.x; k < n; k += 1024) acc += (double)p[k];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     __syncthreads();  // (the previous total has been read)
     if (lane == 0) s[wave] = acc;
     __syncthreads();

@@ -55,29 +55,6 @@ namespace gsr {
 
 // ---- bounds ------------------------------------------------------------------------------------------------------
 
-__device__ inline void pe_block_minmax6(double (&v)[6], double (*s)[6]) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const double u = __shfl_xor(v[k], o, 64);
-            v[k] = k < 3 ? fmin(v[k], u) : fmax(v[k], u);
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) s[wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const double a = s[0][k], b = s[1][k], c = s[2][k], d = s[3][k];
-        v[k] = k < 3 ? fmin(fmin(a, b), fmin(c, d)) : fmax(fmax(a, b), fmax(c, d));
-    }
-    __syncthreads();
-}
-
 // partials [gridDim.x][6]; `final` reduces partials themselves (n rows of 6: min xyz, max xyz)
 __global__ void __launch_bounds__(256) pe_bounds_kernel(long long n, const double* __restrict__ pts, int final,
                                                         double* __restrict__ out) {
@@ -90,7 +67,7 @@ __global__ void __launch_bounds__(256) pe_bounds_kernel(long long n, const doubl
             v[3 + c] = fmax(v[3 + c], final ? pts[6 * i + 3 + c] : pts[3 * i + c]);
         }
     }
-    pe_block_minmax6(v, s);
+    block_minmax6(v, s);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 6; k++) out[6 * blockIdx.x + k] = v[k];

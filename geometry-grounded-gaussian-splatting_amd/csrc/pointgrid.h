@@ -12,6 +12,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "gsr_kernels.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 
@@ -74,12 +75,7 @@ __device__ __forceinline__ uint32_t pe_upper(const uint64_t* __restrict__ keys, 
 // exclusive scan of one value per lane over the 256-lane block; total = the sum
 __device__ __forceinline__ uint32_t pe_block_scan(uint32_t v, uint32_t* s_wave, uint32_t& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
+    const uint32_t inc = wave_incl_scan(v);
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     uint32_t before = 0;

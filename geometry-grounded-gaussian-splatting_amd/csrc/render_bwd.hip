@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(128 / NP) __attribute__((amdgpu_waves_per_eu(N
             on_b[k] = P.inb && P.mDepth.y != 0.f && P.last_b != 0 && !P.cb;
             mine = max(mine, max(on_a[k] ? P.last_a : 0u, on_b[k] ? P.last_b : 0u));
         }
-        const uint32_t wave_last = wave_max_u(mine);
+        const uint32_t wave_last = wave_max(mine);
         const bool block_needs = NP == 2 ? wave_last != 0u : __syncthreads_or(wave_last != 0u);
         uint32_t c = 0;
         int toDo = max_contrib;

@@ -646,7 +646,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SAMPL
     }
 
     // block max of last contributor (cub BlockReduce in the reference)
-    const uint32_t wmax = wave_max_u(last);
+    const uint32_t wmax = wave_max(last);
     if ((tid & 63) == 0) s_max[wave] = wmax;
     __syncthreads();
     if constexpr (!SAMPLE) {
@@ -1989,7 +1989,7 @@ __device__ __forceinline__ void tile_order_body(uint32_t n, const uint32_t* __re
     auto cost = [&](uint32_t t) { return ranges ? ranges[t].y - ranges[t].x : max_contrib[t]; };
     uint32_t m = 0;
     for (uint32_t t = tid; t < n; t += kB) m = max(m, cost(t));
-    m = wave_max_u(m);
+    m = wave_max(m);
     if ((tid & 63) == 0) s_max[tid >> 6] = m;
     s_cnt[tid] = 0u;
     __syncthreads();

@@ -335,7 +335,7 @@ __global__ void __launch_bounds__(kTilePixels / (2 * NPR)) sample_bwd_pairs_kern
             need[q] = on[q] && !cached[q];
             mine = max(mine, need[q] ? last[q] : 0u);
         }
-        const uint32_t wave_last = wave_max_u(mine);
+        const uint32_t wave_last = wave_max(mine);
         const bool block_needs = __syncthreads_or(wave_last != 0u);
         uint32_t c = 0;
         int toDo = max_contrib;
@@ -374,7 +374,7 @@ __global__ void __launch_bounds__(kTilePixels / (2 * NPR)) sample_bwd_pairs_kern
         dpy[k] = {gpy[q0], gpy[q1]};
         mine = max(mine, max(on[q0] ? last[q0] : 0u, on[q1] ? last[q1] : 0u));
     }
-    const uint32_t wave_last = wave_max_u(mine);
+    const uint32_t wave_last = wave_max(mine);
 
     // main pass, front to back (sample_backward.cu:228-354)
     const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;

@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(256)
             fC[o] = counted ? dS_ds12 : 0.f;
         }
     }
-    sum = wave_sum_f(sum);
+    sum = wave_sum(sum);
     if ((tid & 63) == 0) s_red[tid >> 6] = sum;
     __syncthreads();
     if (tid == 0) {
@@ -125,8 +125,7 @@ __global__ void __launch_bounds__(1024) ssim_reduce_kernel(const float* __restri
     double acc = 0.0;
     for (int k = threadIdx.x; k < n; k += 1024) acc += (double)partial[k];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if (lane == 0) s[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {

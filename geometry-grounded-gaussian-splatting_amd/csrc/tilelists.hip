@@ -82,7 +82,8 @@ __device__ __forceinline__ uint32_t scan_len(uint32_t n_host, const uint32_t* n_
 }
 
 // exclusive scan of one value per thread over the block; *total = block sum
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t* total) {
+// (this file's own copies, not gsr_wave.h's: DESIGN.md, "Wave and block primitives", the exceptions)
+__device__ __forceinline__ uint32_t scan_block_excl(uint32_t v, uint32_t* s_w, uint32_t* total) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t x = v;
 #pragma unroll
@@ -103,7 +104,7 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, u
     return before + x - v;
 }
 
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* s_w) {
+__device__ __forceinline__ uint32_t scan_block_sum(uint32_t v, uint32_t* s_w) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -149,7 +150,7 @@ __global__ void __launch_bounds__(kScanThreads)
 #pragma unroll
     for (int k = 0; k < kScanItems; k++) t += v[k];
     uint32_t total;
-    (void)block_excl_scan(t, s_w, &total);
+    (void)scan_block_excl(t, s_w, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -170,9 +171,9 @@ __global__ void __launch_bounds__(kScanThreads)
     // thousand words from L2; cheaper than a separate launch scanning them)
     uint32_t pre = 0;
     for (uint32_t j = threadIdx.x; j < blockIdx.x; j += kScanThreads) pre += sums[j];
-    pre = block_sum(pre, s_w);
+    pre = scan_block_sum(pre, s_w);
     uint32_t total;
-    uint32_t run = pre + block_excl_scan(t, s_w, &total);
+    uint32_t run = pre + scan_block_excl(t, s_w, &total);
     if (i0 + kScanItems <= n) {
         uint4* q = reinterpret_cast<uint4*>(out + i0);
 #pragma unroll
@@ -392,18 +393,9 @@ __global__ void __launch_bounds__(64 * kRowWaves)
     }
 }
 
-// Coalesced emission helper (the tiles pass below).  (The rows
-// pass with the staged emission measured 0.234 -> 0.239 ms at C3, 1.018 -> 1.008
-// at C5: not adopted; its 8-B entries land in only ~5 rows per Gaussian.)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
+// (The rows pass with the tiles pass's staged, coalesced emission measured
+// 0.234 -> 0.239 ms at C3, 1.018 -> 1.008 at C5: not adopted; its 8-B entries
+// land in only ~5 rows per Gaussian.)
 
 // --------------------------------------------------------------- tiles pass
 // Row y's entries are [O_rows[y * nseg_rows], O_rows[(y + 1) * nseg_rows]);

@@ -316,10 +316,7 @@ struct IcpMeans {
 template <int kN>
 __device__ __forceinline__ void icp_block_sum(double (&v)[kN], double (*s)[kIcpMaxSums + 1]) {
 #pragma unroll
-    for (int k = 0; k < kN; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-    }
+    for (int k = 0; k < kN; k++) v[k] = wave_sum(v[k]);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll

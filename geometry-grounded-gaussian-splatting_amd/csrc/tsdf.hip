@@ -198,24 +198,6 @@ __device__ __forceinline__ void mc_neighbours(const uint64_t* __restrict__ keys,
     }
 }
 
-// the exclusive scan of one value per thread over the 256 threads of the workgroup; returns the
-// thread's offset, *total the sum.  s_scan: 256 words.
-__device__ __forceinline__ uint32_t block_scan_256(uint32_t v, uint32_t* s_scan, uint32_t* total) {
-    const int t = threadIdx.x;
-    s_scan[t] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const uint32_t add = t >= d ? s_scan[t - d] : 0u;
-        __syncthreads();
-        s_scan[t] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = s_scan[t];
-    *total = s_scan[255];
-    __syncthreads();
-    return incl - v;
-}
-
 // where voxel (x, y, z), each coordinate in [0, R], of block `b` lives: neighbour n = which
 // coordinates reached R, the linear index there
 template <int R>
@@ -333,7 +315,7 @@ __global__ void __launch_bounds__(256) mc_vertices_kernel(int nb, const uint64_t
                                                           float* __restrict__ vertices,
                                                           float* __restrict__ colors) {
     constexpr int N = R * R * R, PER = N / 256;
-    __shared__ uint32_t s_scan[256];
+    __shared__ uint32_t s_scan[4];
     __shared__ int s_rank[8];
     const int b = blockIdx.x;
     mc_neighbours(keys, nb, b, s_rank);
@@ -345,7 +327,7 @@ __global__ void __launch_bounds__(256) mc_vertices_kernel(int nb, const uint64_t
         mine += __popc(m[k]);
     }
     uint32_t total;
-    uint32_t off = block_scan_256(mine, s_scan, &total);  // (its barriers cover s_rank)
+    uint32_t off = block_excl_scan<4>(mine, s_scan, &total);  // (its barrier covers s_rank)
     const uint64_t key = keys[b];
     const int bx = ((int)(key >> 42 & 0x1fffffu) - kKeyBias) * R, by = ((int)(key >> 21 & 0x1fffffu) - kKeyBias) * R,
               bz = ((int)(key & 0x1fffffu) - kKeyBias) * R;
@@ -391,7 +373,7 @@ __global__ void __launch_bounds__(256) mc_faces_kernel(int nb, const uint64_t* _
                                                        const uint32_t* __restrict__ fbase,
                                                        long long* __restrict__ faces) {
     constexpr int N = R * R * R, PER = N / 256;
-    __shared__ uint32_t s_scan[256];
+    __shared__ uint32_t s_scan[4];
     __shared__ int s_rank[8];
     const int b = blockIdx.x;
     mc_neighbours(keys, nb, b, s_rank);
@@ -402,7 +384,7 @@ __global__ void __launch_bounds__(256) mc_faces_kernel(int nb, const uint64_t* _
         mine += kMcNumTris[c[k]];
     }
     uint32_t total;
-    size_t f = (size_t)fbase[b] + block_scan_256(mine, s_scan, &total);
+    size_t f = (size_t)fbase[b] + block_excl_scan<4>(mine, s_scan, &total);
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         const int nt = kMcNumTris[c[k]];
