@@ -1,5 +1,5 @@
 // gsr_api_common.h — what the translation units of the C ABI layer (gsr_api.hip, api_train.hip,
-// api_mesh.hip, api_eval.hip, api_tnt.hip, api_data.hip) share: the error report, the checking macros and the three host
+// api_mesh.hip, api_eval.hip, api_tnt.hip, api_data.hip, api_model.hip) share: the error report, the checking macros and the three host
 // idioms of an entry point (pinned readback, per-stage event times, scratch carve).  Host code
 // only; not part of the public ABI (include/gsr.h) and included by nothing else.
 #pragma once

@@ -654,4 +654,15 @@ hipError_t launch_image_resample8(long long N, int H, int W, int C, int axis, in
 hipError_t launch_view_planes(long long N, int H, int W, const uint8_t* rgb, const uint8_t* mask, float* original,
                               float* gray, float* gt_mask, hipStream_t stream);
 
+// ---- model files (modelio.hip): the rows of point_cloud.ply <-> the ten stored tensors ----
+// tensors: xyz, features_dc, features_rest, opacity, scaling, rotation, sg_axis, sg_sharpness, sg_color, filter_3D
+int model_row_floats(int M, int G);               // A = 18 + 3 (M - 1) + 7 G; 0: out of range
+int model_block_rows(int A);                      // rows per workgroup of the pack; 0: no row fits the tile
+int model_unpack_block_rows(long long stride);    // rows per workgroup of the unpack; 0: no row fits
+hipError_t launch_model_pack_rows(long long P, int M, int G, const float* const* tensors, float* rows,
+                                  hipStream_t stream);
+hipError_t launch_model_unpack_rows(long long P, int M, int G, long long stride, const uint8_t* rows,
+                                    const int32_t* col_offset, const int32_t* col_type, float* const* tensors,
+                                    hipStream_t stream);
+
 }  // namespace gsr

@@ -161,6 +161,12 @@ SIGNATURES = {
     "gsr_resample_coeffs": (i, [i, i, ip, ip]),
     "gsr_image_resample8": (i, [ll, i, i, i, i, i, vp, vp, vp, vp, vp]),
     "gsr_view_planes": (i, [ll, i, i] + [vp] * 6),
+    # model files
+    "gsr_model_row_floats": (i, [i, i]),
+    "gsr_model_block_rows": (i, [i]),
+    "gsr_model_unpack_block_rows": (i, [ll]),
+    "gsr_model_pack_rows": (i, [ll, i, i] + [vp] * 12),
+    "gsr_model_unpack_rows": (i, [ll, i, i, ll] + [vp] * 14),
     # status
     "gsr_last_error": (c_char_p, []),
     "gsr_abi_version": (i, []),

@@ -122,6 +122,8 @@ class TrainGaussians(torch.nn.Module):
         self.optimizer = FusedAdam([{"params": [p], "lr": lr, "name": nm} for nm, p, lr in groups], lr=0.0,
                                    eps=1e-15)
         self.percent_dense = 0.01  # OptimizationParams.percent_dense (arguments/__init__.py)
+        self.spatial_lr_scale = float(spatial_lr_scale)
+        self._app_lr = {}  # (create_app_model's `lr` overrides, kept for capture())
         self.app_model = gsr_loss.AppModel.NO
         self._appearance_embeddings = None
         self.appearance_network = None
@@ -142,6 +144,7 @@ class TrainGaussians(torch.nn.Module):
         self.app_model = gsr_loss.AppModel(name)
         dev = self._xyz.device
         a = {**self.APP_LR, **(lr or {})}
+        self._app_lr = {k: float(v) for k, v in (lr or {}).items()}
         if name == "no":
             return
         if name == "gs":
@@ -185,6 +188,87 @@ class TrainGaussians(torch.nn.Module):
 
     def reset_opacity(self):
         gsr_densify.reset_opacity(self)
+
+    # ---- files (gaussian_model.py:88-144, 472-493; gsr_model, modelio.hip) ----
+    def save_ply(self, path):
+        import gsr_model
+
+        gsr_model.save_ply(self, path)
+
+    def capture(self):
+        """GaussianModel.capture: the reference's 19 fields in its order (the appearance model as its
+        name, the optimizer's betas as a list), then what this class holds beyond them: filter_3D,
+        xyz_gradient_accum_abs, percent_dense and create_app_model's learning-rate overrides.  Only
+        tensors, numbers, strings, lists, dicts and None; the tensors are the live ones, not copies."""
+        opt = self.optimizer.state_dict()
+        opt = {"state": {k: dict(v) for k, v in opt["state"].items()},
+               "param_groups": [{k: list(v) if isinstance(v, tuple) else v for k, v in g.items()}
+                                for g in opt["param_groups"]]}
+        net = self.appearance_network
+        emb = self._appearance_embeddings
+        return (self.active_sh_degree, self.active_sg_degree, self._xyz.detach(), self._features_dc.detach(),
+                self._features_rest.detach(), self._scaling.detach(), self._rotation.detach(), self._opacity.detach(),
+                self._sg_axis.detach(), self._sg_sharpness.detach(), self._sg_color.detach(), self.max_radii2D,
+                self.xyz_gradient_accum, self.denom, opt, self.spatial_lr_scale, self.app_model.value,
+                None if net is None else {k: v.detach() for k, v in net.state_dict().items()},
+                None if emb is None else emb.detach(),
+                self.filter_3D, self.xyz_gradient_accum_abs, float(self.percent_dense), dict(self._app_lr))
+
+    @torch.no_grad()
+    def restore(self, state):
+        """GaussianModel.restore for capture()'s tuple: every parameter a fresh leaf with the saved bits
+        on this model's device, the optimizer rebuilt with the saved groups (name, learning rate) and
+        per-parameter step / exp_avg / exp_avg_sq, the appearance model's groups with it.  The learning
+        rates are the saved groups'; `spatial_lr_scale` is only recorded, so restore into an object built
+        with the same scale (load_checkpoint does) if anything is to be derived from it later."""
+        (sh, sg, xyz, f_dc, f_rest, scaling, rotation, opacity, sg_axis, sg_sharpness, sg_color, max_radii2D,
+         accum, denom, opt, spatial_lr_scale, app_name, net_state, emb, filter_3D, accum_abs, percent_dense,
+         app_lr) = state
+        dev = self._xyz.device
+        new = lambda t: t.detach().to(dev, copy=True).contiguous()  # noqa: E731
+        self.active_sh_degree, self.active_sg_degree = int(sh), int(sg)
+        saved = {"_xyz": xyz, "_features_dc": f_dc, "_features_rest": f_rest, "_scaling": scaling,
+                 "_rotation": rotation, "_opacity": opacity, "_sg_axis": sg_axis, "_sg_sharpness": sg_sharpness,
+                 "_sg_color": sg_color}
+        for attr, t in saved.items():
+            setattr(self, attr, torch.nn.Parameter(new(t)))
+        self.filter_3D = new(filter_3D)
+        self.max_radii2D, self.xyz_gradient_accum, self.denom = new(max_radii2D), new(accum), new(denom)
+        self.xyz_gradient_accum_abs = new(accum_abs)
+        self.spatial_lr_scale, self.percent_dense = float(spatial_lr_scale), float(percent_dense)
+        self._app_lr = {k: float(v) for k, v in app_lr.items()}
+        self.app_model = gsr_loss.AppModel(app_name)
+        self._appearance_embeddings = None if emb is None else torch.nn.Parameter(new(emb))
+        self.appearance_network = None
+        if net_state is not None:
+            self.appearance_network = gsr_loss.AppearanceNetwork(3 + 64, 3).to(dev)
+            self.appearance_network.load_state_dict(net_state)
+        if self.app_model is gsr_loss.AppModel.GS:
+            a = {**self.APP_LR, **self._app_lr}
+            self.exposure_scheduler_args = _expon_lr(a["gs_init"], a["gs_final"], a["gs_delay_steps"],
+                                                     a["gs_delay_mult"], a["iterations"])
+        attr_of = {name: attr for name, attr, _ in gsr_densify.PARAMS}
+        groups = []
+        for saved_group in opt["param_groups"]:
+            name = saved_group.get("name")
+            if name in attr_of:
+                params = [getattr(self, attr_of[name])]
+            elif name == "appearance_embeddings" and self._appearance_embeddings is not None:
+                params = [self._appearance_embeddings]
+            elif name == "appearance_network" and self.appearance_network is not None:
+                params = list(self.appearance_network.parameters())
+            else:
+                raise ValueError(f"TrainGaussians.restore: optimizer group `{name}` has no parameter in this model")
+            groups.append({"params": params, "lr": saved_group["lr"], "name": name})
+        self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
+        self.optimizer.load_state_dict(
+            {"state": {k: {n: v.detach().clone() if isinstance(v, torch.Tensor) else v for n, v in st.items()}
+                       for k, st in opt["state"].items()},
+             "param_groups": [{k: tuple(v) if k == "betas" else v for k, v in g.items()}
+                              for g in opt["param_groups"]]})
+        for st in self.optimizer.state.values():  # (FusedAdam keeps `step` on the host, as torch's Adam does)
+            if isinstance(st.get("step"), torch.Tensor):
+                st["step"] = st["step"].cpu()
 
     # ---- getters (gaussian_model.py:146-212) ----
     def _cached(self, key, fn):

@@ -1203,6 +1203,59 @@ int gsr_image_resample8(long long N, int H, int W, int C, int axis, int out_size
 int gsr_view_planes(long long N, int H, int W, const uint8_t* rgb, const uint8_t* mask, float* original, float* gray,
                     float* gt_mask, void* stream);
 
+/*
+ * Model files (the reference's save_ply / load_ply, scene/gaussian_model.py:
+ * 450-493 and 541-611): the vertex rows of point_cloud.ply packed from, and
+ * unpacked into, the ten stored tensors
+ *   xyz [P,3], features_dc [P,1,3], features_rest [P,M-1,3], opacity [P,1],
+ *   scaling [P,3], rotation [P,4], sg_axis [P,G,3], sg_sharpness [P,G],
+ *   sg_color [P,G,3], filter_3D [P,1]            (float32, contiguous).
+ * A canonical row is A = gsr_model_row_floats(M, G) = 18 + 3 (M-1) + 7 G
+ * float32 columns in save_ply's property order:
+ *   x y z, nx ny nz (zeros), f_dc_0..2, f_rest_*, opacity, scale_0..2,
+ *   rot_0..3, sg_axis_*, sg_sharpness_*, sg_color_*, filter_3D,
+ * each block the plain flatten of its tensor's row except
+ *   f_rest_{c (M-1) + k} = features_rest[p, k, c]   (transpose(1,2).flatten(1)).
+ * Both kernels copy bits: NaN payloads, -0, infinities and denormals pass.
+ *
+ * gsr_model_row_floats (host only): A, or 0 for M outside [1, 2^20] or G
+ * outside [0, 2^20].
+ * gsr_model_block_rows (host only): the rows one workgroup of the pack kernel
+ * owns for rows of A floats (a block seam falls every that many rows), or 0
+ * when a single row does not fit its tile (A > 8192).
+ *
+ * gsr_model_unpack_block_rows (host only): the same for the unpack kernel and
+ * file rows of `stride` bytes, or 0 when a row does not fit (stride > 32736).
+ *
+ * gsr_model_pack_rows: rows [P,A].  A tensor without columns (features_rest
+ * at M = 1, the sg_* at G = 0) may be NULL.  One launch, no temporaries.
+ *
+ * gsr_model_unpack_rows: the inverse from file rows of `stride` bytes, any
+ * positive number (not necessarily a multiple of 4), at `rows` (16-byte
+ * aligned, P stride bytes; no byte outside them is read).  col_offset and
+ * col_type are DEVICE tables of A entries: the byte offset of each canonical
+ * column inside a file row, -1 for a column the file does not have (it reads
+ * as 0), and its type, 0 = float32 (bits copied) or 1 = float64 (converted
+ * round-to-nearest-even).  Columns nx ny nz are not stored anywhere; their
+ * entries are ignored.  The tables are read back and checked before the
+ * launch (the call waits for `stream` once): an offset below -1, a type other
+ * than 0 or 1, or a column that ends past `stride` is GSR_ERR_ARGS.
+ *
+ * P = 0 is GSR_OK without a launch; a row too long for a tile is
+ * GSR_ERR_ARGS.  Asynchronous on `stream` but for the table check.
+ */
+int gsr_model_row_floats(int M, int G);
+int gsr_model_block_rows(int A);
+int gsr_model_unpack_block_rows(long long stride);
+int gsr_model_pack_rows(long long P, int M, int G, const float* xyz, const float* features_dc,
+                        const float* features_rest, const float* opacity, const float* scaling, const float* rotation,
+                        const float* sg_axis, const float* sg_sharpness, const float* sg_color, const float* filter_3D,
+                        float* rows, void* stream);
+int gsr_model_unpack_rows(long long P, int M, int G, long long stride, const uint8_t* rows, const int32_t* col_offset,
+                          const int32_t* col_type, float* xyz, float* features_dc, float* features_rest,
+                          float* opacity, float* scaling, float* rotation, float* sg_axis, float* sg_sharpness,
+                          float* sg_color, float* filter_3D, void* stream);
+
 /* Human-readable message for the last non-OK status on this thread. */
 const char* gsr_last_error(void);
 
